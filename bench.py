@@ -9,7 +9,20 @@ Y.backward(dY) (projections, edge kernels, every weight / input gradient).  The 
 build) is outside the timed region, as DGL's cached CSC is.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--graph S2|S1|S1u|arxiv] [--agg sum|mean|sym]
-                  [--dtype f32|bf16|f16] [--workload cfg4|cfg1|cfg2|cfg3|cfg5]
+                  [--dtype f32|bf16|f16] [--workload cfg4|cfg1|cfg2|cfg3|cfg5] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, EXACTLY K timed steps,
+one JSON line (``value``, ``ms_per_step`` = the mean over the K bracketed steps, the per-step median
+beside them).  ``--full`` adds everything else the benchmark measures, each as it was before the
+option existed: per-kernel HIP-event times and the ``roofline`` / ``projections`` /
+``design_bytes_per_step`` tables built from them, the streaming-copy rate, the torch-fp32-GEMM A/B
+step, the stack workloads' eager per-kernel steps and the ``cpu_baseline``.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step computed — the arrays a
+caller of the layer receives: ``Y``, ``dX`` and every parameter gradient — as ``DIR/<name>.npy`` in
+float32.  Arrays above a per-array budget are reduced to a fixed, seeded sample of their rows (the
+same rows in every run; at most 64 MB in all).  Inputs, weights and the graph are seeded on the host,
+so two builds run with the same arguments can be compared array for array.
 
 * ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process starts
   ``torch.distributed.run`` with N ranks (before touching the GPU) and exits with its status;
@@ -20,7 +33,7 @@ build) is outside the timed region, as DGL's cached CSC is.
 * Without a GPU (``--dist-backend gloo``) the edge-cut plumbing is rehearsed on the CPU with the
   test-only CPU edge backend: the line is marked ``"rehearsal"`` and measures nothing.
 
-Prints ONE JSON line (rank 0).  ``roofline``: the forward edge-aggregation kernel (the kernel the
+Prints ONE JSON line (rank 0).  With ``--full``: ``roofline``: the forward edge-aggregation kernel (the kernel the
 north star names), SURVEY §8(d) algorithmic bytes ÷ its mean launch time from HIP events on the
 launching stream; plus the PMC-counter and unique-bytes views and a streaming-copy rate measured in
 the same process.  ``cpu_baseline``: the reference CPU dataflow restated in ``oracle/`` (DGL
@@ -66,10 +79,16 @@ def parse():
     ap.add_argument("--dropout", type=float, default=None,
                     help="SIRConv feat_dropout (Q/K dropout, conv.py:60-61) in training mode; default: 0 for cfg4, "
                          "the reference's trained value for the stack workloads (cfg3 / cfg5: 0.2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times, roofline, copy rate, "
+                         "torch-GEMM A/B, the stack workloads' eager per-kernel steps, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (Y, dX, parameter gradients) as DIR/<name>.npy "
+                         "(float32; a fixed seeded row sample of large arrays, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-graph", default="S1", help="graph of the reference CPU dataflow baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="repeat CPU baseline steps until this long")
-    ap.add_argument("--no-aux", action="store_true", help="skip the copy-rate and torch-GEMM A/B measurements")
+    ap.add_argument("--no-aux", action="store_true", help="--full without the copy-rate and torch-GEMM A/B measurements")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) for real runs; gloo to rehearse N ranks (CPU without a GPU)")
     ap.add_argument("--force-dist", action="store_true",
@@ -246,9 +265,10 @@ def kernel_table(timing, rows_of, edges, H, agg, masked, s):
 STEP_MS = []       # per-step times (ms) of the last timed_loop, from HIP events between steps
 
 
-def timed_loop(step, steps, warmup, world, dist, dev):
+def timed_loop(step, steps, warmup, world, dist, dev, per_kernel=True):
     """Time EXACTLY ``steps`` steps between barrier + synchronize; per-step HIP events on the
-    current stream (no host sync inside the loop) give the median beside the mean."""
+    current stream (no host sync inside the loop) give the median beside the mean.
+    ``per_kernel`` (--full): HIP events around every native call as well (the kernel tables)."""
     import torch
     from sirgcn import _native
     for _ in range(warmup):
@@ -256,7 +276,7 @@ def timed_loop(step, steps, warmup, world, dist, dev):
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
-    timing = _native.enable_timing(True)
+    timing = _native.enable_timing(True) if per_kernel else {}
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     t0 = time.perf_counter()
     evs[0].record()
@@ -284,6 +304,39 @@ def max_over_ranks(x, world, dist, dev):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return t.item()
+
+
+# ------------------------------------------------------------------------------ outputs
+DUMP_TOTAL = 60 << 20      # bytes of float32 over all arrays (the contract: at most 64 MB)
+DUMP_ARRAY = 16 << 20      # per-array budget before the total is divided
+
+
+def step_outputs(Y, X, module):
+    """What a caller of the timed step receives: Y, dX and every parameter gradient (live tensors)."""
+    out = {"Y": Y.detach(), "dX": X.grad}
+    for n, p in module.named_parameters():
+        if p.grad is not None:
+            out["grad_" + n.replace(".", "_")] = p.grad
+    return out
+
+
+def dump_outputs(path, tensors):
+    """``path/<name>.npy`` (float32) of each tensor; an array above the budget is reduced to a fixed
+    sample of its rows (seeded by the array's shape alone: the same rows in every run and build)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    budget = min(DUMP_ARRAY, DUMP_TOTAL // max(len(tensors), 1))
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        row_bytes = 4 * max(t[0].numel(), 1) if t.shape[0] else 4
+        keep = max(budget // row_bytes, 1)
+        if t.shape[0] > keep:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(t.shape[0]))[:keep]
+            t = t.index_select(0, rows.sort().values.to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 # ------------------------------------------------------------------------------ main
@@ -342,7 +395,13 @@ def run_edge_cut(args, world, rank, dev, rehearsal, torch, dist, nn):
     dtn = args.dtype or "f32"
     dt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[dtn]
     V, E, alpha = NAMED[args.graph]
-    src, dst = powerlaw_edges(V, E, alpha, seed=0)
+    # host-side inputs, each from a generator of its own: drawn side by side (the same values as in turn)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(3) as pool:
+        f_edges = pool.submit(powerlaw_edges, V, E, alpha, seed=0)
+        f_X = pool.submit(lambda: torch.randn(V, H, generator=torch.Generator().manual_seed(3)))
+        f_dY = pool.submit(lambda: torch.randn(V, H, generator=torch.Generator().manual_seed(5)))
+        (src, dst), X_full, dY_full = f_edges.result(), f_X.result(), f_dY.result()
 
     torch.manual_seed(4)
     p_drop = args.dropout or 0.0
@@ -355,8 +414,6 @@ def run_edge_cut(args, world, rank, dev, rehearsal, torch, dist, nn):
             EdgeMaxLinear.hybrid_bwd = False
     if args.chunk:
         conv.chunk = args.chunk
-    X_full = torch.randn(V, H, generator=torch.Generator().manual_seed(3))
-    dY_full = torch.randn(V, H, generator=torch.Generator().manual_seed(5))
 
     dconv = None
     if world == 1 and not args.force_dist and not rehearsal:
@@ -397,11 +454,18 @@ def run_edge_cut(args, world, rank, dev, rehearsal, torch, dist, nn):
         Y.backward(dY_in if dY_in.dtype == Y.dtype else dY_in.to(Y.dtype))
         if dconv is not None:
             dconv.allreduce_grads()
+        if args.dump_outputs:
+            last["Y"] = Y
 
+    last = {}
+    full = args.full
     if rehearsal:
         el, timing = rehearsal_loop(step, args.steps, args.warmup, world, dist)
     else:
-        el, timing = timed_loop(step, args.steps, args.warmup, world, dist, dev)
+        el, timing = timed_loop(step, args.steps, args.warmup, world, dist, dev, per_kernel=full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(last["Y"], X, conv))
+    last.clear()
     el = max_over_ranks(el, world, dist, dev if args.dist_backend == "nccl" and not rehearsal else "cpu")
     med = None if rehearsal else max_over_ranks(median(STEP_MS), world, dist,
                                                 dev if args.dist_backend == "nccl" else "cpu")
@@ -425,6 +489,17 @@ def run_edge_cut(args, world, rank, dev, rehearsal, torch, dist, nn):
     # the bracketed K steps (the bench contract)
     out["ms_per_step_median"] = round(med, 3)
     out["value_median"] = round(E / (med * 1e-3), 1)
+    if dconv is not None:     # halo exchange volume per rank (rows of H), max over ranks
+        s = SIZEOF[dtn]
+        ex = torch.tensor([dg.n_halo, dg.exchange_rows()[1], edges_local], dtype=torch.float64,
+                          device=dev if args.dist_backend == "nccl" else "cpu")
+        if world > 1:
+            dist.all_reduce(ex, op=dist.ReduceOp.MAX)
+        out["exchange"] = {"halo_rows_max": int(ex[0]), "send_rows_max": int(ex[1]), "local_edges_max": int(ex[2]),
+                           "bytes_per_direction_max": int(ex[0]) * H * s, "exchange_chunks": dg.chunks,
+                           "dense_allgather_rows": V - min(dg.bounds[i + 1] - dg.bounds[i] for i in range(world))}
+    if not full:
+        return out
     from sirgcn.conv import EdgeAggregate
     s = SIZEOF[dtn]
     masked = bool(EdgeAggregate.use_mask and _native.mask_words(H, _native.ACT_LEAKY)) and args.agg != "max"
@@ -453,14 +528,6 @@ def run_edge_cut(args, world, rank, dev, rehearsal, torch, dist, nn):
     if gemm:
         out["projections"] = projections(gemm, args.steps)
     out["design_bytes_per_step"] = design_bytes(kernels, gemm, args.steps, ms)
-    if dconv is not None:     # halo exchange volume per rank (rows of H), max over ranks
-        ex = torch.tensor([dg.n_halo, dg.exchange_rows()[1], edges_local], dtype=torch.float64,
-                          device=dev if args.dist_backend == "nccl" else "cpu")
-        if world > 1:
-            dist.all_reduce(ex, op=dist.ReduceOp.MAX)
-        out["exchange"] = {"halo_rows_max": int(ex[0]), "send_rows_max": int(ex[1]), "local_edges_max": int(ex[2]),
-                           "bytes_per_direction_max": int(ex[0]) * H * s, "exchange_chunks": dg.chunks,
-                           "dense_allgather_rows": V - min(dg.bounds[i + 1] - dg.bounds[i] for i in range(world))}
     if world == 1 and not args.no_aux:
         out["roofline"]["copy_GBps_measured"] = copy_rate(dev)
         if not args.torch_gemm and dtn == "f32":        # IEEE fp32 projections (torch / hipBLASLt) beside it
@@ -579,9 +646,15 @@ def rehearse_stack(args, world, rank, dev, torch, dist):
     def step():
         model.zero_grad(set_to_none=True)
         X.grad = None
-        model(g, X).backward(dY)
+        Y = model(g, X)
+        Y.backward(dY)
+        if args.dump_outputs:
+            last["Y"] = Y
 
+    last = {}
     el, _ = rehearsal_loop(step, args.steps, args.warmup, world, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(last["Y"], X, stack))
     tot = torch.tensor([g.num_edges(), g.num_nodes(), g.batch_size], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tot)
@@ -622,7 +695,11 @@ def run_stack(args, world, rank, dev, torch, dist):
         else:
             Y = model(g, X)
         Y.backward(dY_in if dY_in.dtype == Y.dtype else dY_in.to(Y.dtype))
+        if args.dump_outputs:
+            last["Y"] = Y
 
+    last = {}
+    full = args.full
     # Batched small graphs are launch-bound (SURVEY §7 "tiny batched graphs"): at N = 1 the whole
     # fwd+bwd step (every kernel, every ctypes launch, the allocator's work) is captured once into
     # a HIP graph and replayed; per-kernel HIP-event timing is then measured on the eager step.
@@ -639,11 +716,20 @@ def run_stack(args, world, rank, dev, torch, dist):
         with torch.cuda.graph(captured):
             step()
         torch.cuda.synchronize(dev)
+    timing = {}
     if captured is not None:
-        _, timing = timed_loop(step, 3, 1, world, dist, dev)          # eager: per-kernel events
-        el, _ = timed_loop(captured.replay, args.steps, args.warmup, world, dist, dev)
+        # the captured step's output tensors: every replay writes its results into these
+        outs = step_outputs(last["Y"], X, stack) if args.dump_outputs else None
+        if full:
+            _, timing = timed_loop(step, 3, 1, world, dist, dev)      # eager: per-kernel events
+        el, _ = timed_loop(captured.replay, args.steps, args.warmup, world, dist, dev, per_kernel=False)
     else:
-        el, timing = timed_loop(step, args.steps, args.warmup, world, dist, dev)
+        el, timing = timed_loop(step, args.steps, args.warmup, world, dist, dev, per_kernel=full)
+        outs = step_outputs(last["Y"], X, stack) if args.dump_outputs else None
+    if outs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
+    outs = None
+    last.clear()
     el = max_over_ranks(el, world, dist, dev)
     med = max_over_ranks(median(STEP_MS), world, dist, dev)
     L, H, E, V = c["layers"], c["hidden"], g.num_edges(), g.num_nodes()
@@ -651,10 +737,6 @@ def run_stack(args, world, rank, dev, torch, dist):
     if world > 1:
         dist.all_reduce(tot)
     E_all, V_all, B_all = (int(x) for x in tot.tolist())
-    from sirgcn.conv import EdgeAggregate
-    masked = bool(EdgeAggregate.use_mask and _native.mask_words(H, _native.ACT_LEAKY))
-    kernels, gemm = kernel_table(timing, lambda n: V, E, H, c["agg"], masked, SIZEOF[dtn])
-    eager_steps = 3 if captured is not None else args.steps
     out = {"metric": "layer-edges/sec SIRConv stack fwd+bwd (E x layers / step time)",
            "value": round(E_all * L / (el / args.steps), 1), "unit": "edges/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3),
@@ -664,7 +746,14 @@ def run_stack(args, world, rank, dev, torch, dist):
                                   f"{' per rank, DDP over RCCL' if world > 1 else ''}",
                       "graphs_per_s": round(B_all / (el / args.steps), 1), "V_total": V_all, "E_total": E_all,
                       "parallelism": f"data-parallel x{world}" if world > 1 else "single GPU"},
-           "ms_per_step_median": round(med, 3), "kernels": kernels, "hip_graph": captured is not None}
+           "ms_per_step_median": round(med, 3), "hip_graph": captured is not None}
+    if not full:
+        return out
+    from sirgcn.conv import EdgeAggregate
+    masked = bool(EdgeAggregate.use_mask and _native.mask_words(H, _native.ACT_LEAKY))
+    kernels, gemm = kernel_table(timing, lambda n: V, E, H, c["agg"], masked, SIZEOF[dtn])
+    eager_steps = 3 if captured is not None else args.steps
+    out["kernels"] = kernels
     if captured is not None:
         out["kernels_note"] = "per-kernel times from 3 eager steps; value / ms_per_step from the replayed HIP graph"
     if gemm:

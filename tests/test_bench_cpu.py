@@ -6,15 +6,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 from conftest import ROOT
 
 
-def test_bench_self_launches_n_ranks_without_world_size():
+def test_bench_self_launches_n_ranks_without_world_size(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
                                                              "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "2"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--graph", "S1", "--hidden", "8", "--steps", "1", "--warmup", "0"]
+           "--graph", "S1", "--hidden", "8", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -24,6 +26,13 @@ def test_bench_self_launches_n_ranks_without_world_size():
     assert out["metric"] == "edges/sec SIRConv fwd+bwd, d_hidden=256, 1/2/4/8 MI355X"
     assert out["config"]["E"] == 10_000_000 and "edge-cut" in out["config"]["parallelism"]
     assert "rehearsal" in out                   # no GPU here: plumbing only, not a measurement
+    assert out["ms_per_step"] > 0 and "roofline" not in out and "cpu_baseline" not in out
+    # --dump-outputs: the last step's Y, dX and parameter gradients (rank 0's rows), float32, <= 64 MB
+    dumped = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert {"Y", "dX", "grad_linear_query_weight", "grad_linear_key_weight", "grad_linear_relation_weight"} <= set(dumped)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dumped.values())
+    assert dumped["Y"].shape[1] == 8 and dumped["Y"].shape == dumped["dX"].shape
+    assert sum(a.nbytes for a in dumped.values()) <= 64 * 10 ** 6
 
 
 def test_bench_refuses_mismatched_world_size():

@@ -4,7 +4,7 @@
 #   a pass on gfx950), then per-launch HBM bytes -> profiles/pmc_traffic.json.
 set -e
 OUT=${1:-gpurun_out}
-ARGS=${BENCH_ARGS:-"--steps 5 --warmup 2 --no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--full --steps 5 --warmup 2 --no-cpu-baseline"}
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py $ARGS > "$OUT/prof.log" 2>&1

@@ -10,6 +10,9 @@
  * Entry points, by the reference code they replace (INTEGRATION.md §2 has the table):
  *  - the edge aggregation and its backward (conv.py:43-45,63): sir_edge_agg_fwd / _bwd_dst /
  *    _bwd_src / _bwd (one launch), with the sign mask of the ReLU family (sir_mask_words);
+ *  - SIREConv's edge term inside sigma (conv.py:108-113,128-131): sir_edge_e_agg_fwd (the forward with
+ *    one extra gathered edge row per edge) and sir_edge_e_bwd (the edge term's gradient); dQ / dK come
+ *    from the sign-mask passes above, unchanged;
  *  - the degree norms (conv.py:51-57): sir_degree_norms;
  *  - the projections and their gradients (nn.Linear, conv.py:60-61,65): the split-fp16 MFMA
  *    GEMMs sir_gemm_nt / sir_gemm_nt_direct / sir_gemm_tn and the 16-bit (autocast) ones, the
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define SIR_ABI_VERSION 16
+#define SIR_ABI_VERSION 17
 
 /* aggregation: conv.py:41 (`sym` -> fn.sum with deg^-1/2 norms conv.py:54-57).  SIR_AGG_ACCUMULATE,
  * OR'd into the forward's `agg` (SUM / SYM): S[v] = S[v] + the sum over the given items' edges, rows
@@ -213,6 +216,44 @@ int sir_edge_agg_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* i
                      const float* in_norm, const float* out_norm, int agg, int act, float slope,
                      void* dQ, int64_t lddq, void* dK, int64_t lddk, float* partial, float* partial_s,
                      const sir_dropout_t* drop, void* stream);
+
+/*
+ * SIREConv forward edge aggregation (ABI 17) — replaces the message UDF and update_all of conv.py:109-113,128
+ * (m = out_norm[u] * in_norm[v] * sigma(eq[v] + ek[u] + e_uv), reduced by sum / mean) without an [E, H]
+ * tensor.  For the edge at destination-CSR position p of row v, with u = col[p]:
+ *   z_p = (Q[v] + K[u]) + Eh[r(p)],   r(p) = eidx ? eidx[p] : p   (two fp32 adds in this order),
+ *   S[v] = sum_p c_p * sigma(z_p),    c_p and the MEAN division as sir_edge_agg_fwd,
+ * summed in edge order (split rows: `partial` + the combine of sir_edge_agg_fwd).
+ *   Eh: [n_erows, H] (lde) fp32 edge rows — the projected edge features in any order with eidx the
+ *   map from CSR position to row (a permutation: the caller's edge order; or ids into a small table
+ *   such as an nn.Embedding weight), or already in destination-CSR order with eidx = NULL.  Ids are
+ *   clamped into [0, n_erows): a bad id reads a wrong row, never out of bounds.
+ *   mask_out: NULL, or E * sir_mask_words(H, act) words receiving the sign of THIS z in the layout
+ *   sir_mask_words documents — sir_edge_agg_bwd / _bwd_dst / _bwd_src in sign-mask mode then give
+ *   dQ and dK, and sir_edge_e_bwd the edge term's gradient.
+ * Supported: SIR_DTYPE_F32, act RELU / LEAKY_RELU, SUM / MEAN / SYM, H % 4 == 0, 4 <= H <= 1024, 16-B
+ * aligned rows (pointers and leading dimensions); anything else returns SIR_EUNSUPPORTED.
+ */
+int sir_edge_e_agg_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
+                       const int32_t* splits, int64_t n_splits, int64_t H, int dtype,
+                       const void* Q, int64_t ldq, const void* K, int64_t ldk,
+                       const void* Eh, int64_t lde, int64_t n_erows, const int32_t* eidx,
+                       const float* norm_row, const float* norm_col, int agg, int act, float slope,
+                       void* S, int64_t lds, uint64_t* mask_out, float* partial, void* stream);
+
+/*
+ * SIREConv backward, edge term (ABI 17) — the e_uv branch of autograd through conv.py:109-113,128:
+ *   dE[r(p)] = bit_p ? t_p : (RELU ? 0 : t_p * slope),   t_p = G[v] (SUM) or G[v] * (norm_col[u] * norm_row[v]) (SYM)
+ * for every destination-CSR position p (row v, u = col[p]); bit_p = the forward's sign mask.  MEAN: pass
+ * G already divided by max(deg, 1) with agg = SUM (as for sir_edge_agg_bwd).  Every edge writes one
+ * row: with eidx a permutation (or NULL: destination-CSR order) dE is fully overwritten; no partial
+ * workspace, no combine.  rowptr / col / items: the destination CSR and its plan.  Same support
+ * limits as sir_edge_e_agg_fwd.
+ */
+int sir_edge_e_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
+                   int64_t H, int dtype, const uint64_t* mask, const void* G, int64_t ldg,
+                   const float* norm_row, const float* norm_col, int agg, int act, float slope,
+                   const int32_t* eidx, int64_t n_erows, void* dE, int64_t ldde, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Edge-materialised path: agg_type='max' (conv.py:46-47 + DGL max reduce) and sigma callables the

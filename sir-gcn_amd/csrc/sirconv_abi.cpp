@@ -11,6 +11,7 @@
 
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_eedge.h"
 
 namespace {
 
@@ -257,6 +258,72 @@ int sir_edge_agg_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* i
     const char* why = nullptr;
     hipError_t err = sir::run_edge_dual(dtype, a, splits, n_splits, b, splits_s, n_splits_s, agg, act,
                                         static_cast<hipStream_t>(stream), &why);
+    return finish(fn, err, why);
+}
+
+// ------------------------------------------------------------------------------ SIREConv edge term
+static int check_eedge(const char* fn, int64_t H, int dtype, int act) {
+    if (dtype != SIR_DTYPE_F32) return fail(SIR_EUNSUPPORTED, fn, "the edge-term kernels take SIR_DTYPE_F32 rows only");
+    if (act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
+        return fail(SIR_EUNSUPPORTED, fn, "the edge-term kernels cover act RELU / LEAKY_RELU only");
+    if (H % 4 != 0) return fail(SIR_EUNSUPPORTED, fn, "the edge-term kernels need H % 4 == 0");
+    return SIR_OK;
+}
+
+int sir_edge_e_agg_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
+                       const int32_t* splits, int64_t n_splits, int64_t H, int dtype,
+                       const void* Q, int64_t ldq, const void* K, int64_t ldk,
+                       const void* Eh, int64_t lde, int64_t n_erows, const int32_t* eidx,
+                       const float* norm_row, const float* norm_col, int agg, int act, float slope,
+                       void* S, int64_t lds, uint64_t* mask_out, float* partial, void* stream) {
+    const char* fn = "sir_edge_e_agg_fwd";
+    int rc = check_common(fn, rowptr, col, items, n_items, splits, n_splits, H, dtype, agg, act,
+                          norm_row, norm_col, S, partial);
+    if (rc) return rc;
+    if ((rc = check_eedge(fn, H, dtype, act))) return rc;
+    if (ldq < H || ldk < H || lde < H || lds < H) return fail(SIR_EINVAL, fn, "leading dimensions must be >= H");
+    if (n_items > INT32_MAX || n_erows > INT32_MAX) return fail(SIR_EINVAL, fn, "too many work items / edge rows");
+    if (n_items > 0 && (Q == nullptr || K == nullptr || Eh == nullptr))
+        return fail(SIR_EINVAL, fn, "Q/K/Eh must be non-NULL");
+    if (n_items > 0 && n_erows <= 0) return fail(SIR_EINVAL, fn, "n_erows must be positive");
+    if (n_items == 0) return SIR_OK;
+    sir::EEdgeArgs a{};
+    a.rowptr = rowptr; a.col = col; a.items = items; a.n_items = n_items; a.splits = splits; a.n_splits = n_splits;
+    a.H = (int)H;
+    a.Q = static_cast<const float*>(Q); a.ldq = ldq;
+    a.K = static_cast<const float*>(K); a.ldk = ldk;
+    a.Eh = static_cast<const float*>(Eh); a.lde = lde; a.n_erows = n_erows; a.eidx = eidx;
+    a.norm_row = norm_row; a.norm_col = norm_col; a.slope = slope;
+    a.S = static_cast<float*>(S); a.lds = lds; a.mask_out = mask_out; a.partial = partial;
+    const char* why = nullptr;
+    hipError_t err = sir::run_eedge_fwd(a, agg, act, static_cast<hipStream_t>(stream), &why);
+    return finish(fn, err, why);
+}
+
+int sir_edge_e_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
+                   int64_t H, int dtype, const uint64_t* mask, const void* G, int64_t ldg,
+                   const float* norm_row, const float* norm_col, int agg, int act, float slope,
+                   const int32_t* eidx, int64_t n_erows, void* dE, int64_t ldde, void* stream) {
+    const char* fn = "sir_edge_e_bwd";
+    int rc = check_common(fn, rowptr, col, items, n_items, nullptr, 0, H, dtype, agg, act,
+                          norm_row, norm_col, dE, nullptr);
+    if (rc) return rc;
+    if (agg == SIR_AGG_MEAN)
+        return fail(SIR_EUNSUPPORTED, fn, "MEAN: call with SUM on g = G / deg (as the one-launch backward)");
+    if ((rc = check_eedge(fn, H, dtype, act))) return rc;
+    if (ldg < H || ldde < H) return fail(SIR_EINVAL, fn, "leading dimensions must be >= H");
+    if (n_items > INT32_MAX || n_erows > INT32_MAX) return fail(SIR_EINVAL, fn, "too many work items / edge rows");
+    if (n_items > 0 && (mask == nullptr || G == nullptr)) return fail(SIR_EINVAL, fn, "mask/G must be non-NULL");
+    if (n_items > 0 && n_erows <= 0) return fail(SIR_EINVAL, fn, "n_erows must be positive");
+    if (n_items == 0) return SIR_OK;
+    sir::EEdgeArgs a{};
+    a.rowptr = rowptr; a.col = col; a.items = items; a.n_items = n_items;
+    a.H = (int)H; a.mask_in = mask;
+    a.G = static_cast<const float*>(G); a.ldg = ldg;
+    a.norm_row = norm_row; a.norm_col = norm_col; a.slope = slope;
+    a.eidx = eidx; a.n_erows = n_erows; a.dE = static_cast<float*>(dE); a.ldde = ldde;
+    const char* why = nullptr;
+    hipError_t err = sir::run_eedge_bwd_e(a, agg, act, static_cast<hipStream_t>(stream), &why);
     return finish(fn, err, why);
 }
 

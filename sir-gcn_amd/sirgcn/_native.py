@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SIRGCN_LIB") or os.path.join(os.path.dirname(os.path.
 AGG = {"sum": 0, "mean": 1, "sym": 2}
 ACT_IDENTITY, ACT_RELU, ACT_LEAKY, ACT_GELU, ACT_GELU_TANH = range(5)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
-ABI_VERSION = 16
+ABI_VERSION = 17
 STORAGE = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}
 
 # exported symbol -> (restype, argtypes); mirrors include/sirconv.h
@@ -100,6 +100,10 @@ SIGNATURES = {
                                             _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _I64, _P, _P]),
     "sir_edge_agg_bwd": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I, _P,
                                         _P, _I64, _P, _P, _I, _I, _F, _P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "sir_edge_e_agg_fwd": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I64, _I, _P, _I64, _P, _I64, _P, _I64, _I64, _P,
+                                          _P, _P, _I, _I, _F, _P, _I64, _P, _P, _P]),
+    "sir_edge_e_bwd": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I, _P, _P, _I64, _P, _P, _I, _I, _F, _P, _I64, _P, _I64,
+                                      _P]),
 }
 
 class Dropout(ctypes.Structure):
@@ -336,6 +340,37 @@ def edge_agg_bwd(csr, csr_s, G, mask, in_norm, out_norm, agg, act, slope, dQ, dK
             _ptr(csr_s.splits), csr_s.n_splits, H, _storage(G, dQ, dK), _ptr(mask), _ptr(G), _ld(G, H),
             _ptr(in_norm), _ptr(out_norm), AGG[agg], act, float(slope), _ptr(dQ), _ld(dQ, H), _ptr(dK), _ld(dK, H),
             _ptr(partial), _ptr(partial_s), _drop(drop), _stream(dQ.device))
+    _check(rc, lib)
+
+
+# ------------------------------------------------------------------------------ SIREConv edge term
+def edge_e_agg_fwd(csr, Q, K, Eh, eidx, norm_row, norm_col, agg, act, slope, S, partial, mask_out=None):
+    """S[v] = sum_p c_p sigma((Q[v] + K[u]) + Eh[r(p)]), r(p) = eidx[p] (int32, dst-CSR order) or p when
+    ``eidx`` is None; ``mask_out`` receives the sign of this z in the ``sir_mask_words`` layout."""
+    lib = load()
+    H = S.shape[1]
+    if eidx is not None and not (eidx.dtype == torch.int32 and eidx.is_contiguous() and eidx.numel() == csr.col.numel()):
+        raise ValueError("eidx must be a contiguous int32 tensor with one entry per edge")
+    with _Timed("sir_edge_e_agg_fwd", S.device):
+        rc = lib.sir_edge_e_agg_fwd(
+            _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.items), csr.n_items, _ptr(csr.splits), csr.n_splits,
+            H, _storage(Q, K, Eh, S), _ptr(Q), _ld(Q, H), _ptr(K), _ld(K, H), _ptr(Eh), _ld(Eh, H), Eh.shape[0],
+            _ptr(eidx), _ptr(norm_row), _ptr(norm_col), AGG[agg], act, float(slope), _ptr(S), _ld(S, H),
+            _ptr(mask_out), _ptr(partial), _stream(S.device))
+    _check(rc, lib)
+
+
+def edge_e_bwd(csr, mask, G, norm_row, norm_col, agg, act, slope, eidx, dE):
+    """dE[r(p)] = sigma'(z_p) t_p from the forward's sign mask (SUM / SYM; MEAN: pass G / deg with 'sum')."""
+    lib = load()
+    H = dE.shape[1]
+    if eidx is not None and not (eidx.dtype == torch.int32 and eidx.is_contiguous() and eidx.numel() == csr.col.numel()):
+        raise ValueError("eidx must be a contiguous int32 tensor with one entry per edge")
+    with _Timed("sir_edge_e_bwd", dE.device):
+        rc = lib.sir_edge_e_bwd(
+            _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.items), csr.n_items, H, _storage(G, dE), _ptr(mask),
+            _ptr(G), _ld(G, H), _ptr(norm_row), _ptr(norm_col), AGG[agg], act, float(slope), _ptr(eidx),
+            dE.shape[0], _ptr(dE), _ld(dE, H), _stream(dE.device))
     _check(rc, lib)
 
 

@@ -66,6 +66,33 @@ int main() {
     expect("bwd (one launch): needs mask", sir_edge_agg_bwd(p, p, p, 1, nullptr, 0, p, p, p, p, 1, nullptr, 0, 256, 0,
                                                              nullptr, v, 256, nullptr, nullptr, 0, 2, 0.2f, v, 256, v, 256,
                                                              nullptr, nullptr, nullptr, nullptr), SIR_EINVAL, "mask");
+    // SIREConv edge term
+    expect("e_fwd: 16-bit storage", sir_edge_e_agg_fwd(p, p, p, 1, nullptr, 0, 16, 1, v, 16, v, 16, v, 16, 1, nullptr,
+                                                       nullptr, nullptr, 0, 2, 0.2f, v, 16, nullptr, nullptr, nullptr),
+           SIR_EUNSUPPORTED, "F32");
+    expect("e_fwd: GELU", sir_edge_e_agg_fwd(p, p, p, 1, nullptr, 0, 16, 0, v, 16, v, 16, v, 16, 1, nullptr, nullptr,
+                                             nullptr, 0, 3, 0.f, v, 16, nullptr, nullptr, nullptr), SIR_EUNSUPPORTED, "RELU");
+    expect("e_fwd: NULL Eh", sir_edge_e_agg_fwd(p, p, p, 1, nullptr, 0, 16, 0, v, 16, v, 16, nullptr, 16, 1, nullptr,
+                                                nullptr, nullptr, 0, 2, 0.2f, v, 16, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "Q/K/Eh");
+    expect("e_fwd: lde < H", sir_edge_e_agg_fwd(p, p, p, 1, nullptr, 0, 16, 0, v, 16, v, 16, v, 8, 1, nullptr, nullptr,
+                                                nullptr, 0, 2, 0.2f, v, 16, nullptr, nullptr, nullptr), SIR_EINVAL, "leading");
+    expect("e_fwd: no edge rows", sir_edge_e_agg_fwd(p, p, p, 1, nullptr, 0, 16, 0, v, 16, v, 16, v, 16, 0, nullptr,
+                                                     nullptr, nullptr, 0, 2, 0.2f, v, 16, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "n_erows");
+    expect("e_fwd: SYM without norms", sir_edge_e_agg_fwd(p, p, p, 1, nullptr, 0, 16, 0, v, 16, v, 16, v, 16, 1, nullptr,
+                                                          nullptr, nullptr, 2, 2, 0.2f, v, 16, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "SYM");
+    expect("e_fwd: empty work is a no-op", sir_edge_e_agg_fwd(nullptr, nullptr, nullptr, 0, nullptr, 0, 256, 0, nullptr,
+                                                             256, nullptr, 256, nullptr, 256, 0, nullptr, nullptr, nullptr,
+                                                             0, 2, 0.2f, nullptr, 256, nullptr, nullptr, nullptr), SIR_OK);
+    expect("e_bwd: MEAN refused", sir_edge_e_bwd(p, p, p, 1, 16, 0, reinterpret_cast<uint64_t*>(v), v, 16, nullptr, nullptr,
+                                                 1, 2, 0.2f, nullptr, 1, v, 16, nullptr), SIR_EUNSUPPORTED, "MEAN");
+    expect("e_bwd: NULL mask", sir_edge_e_bwd(p, p, p, 1, 16, 0, nullptr, v, 16, nullptr, nullptr, 0, 2, 0.2f, nullptr, 1,
+                                              v, 16, nullptr), SIR_EINVAL, "mask/G");
+    expect("e_bwd: empty work is a no-op", sir_edge_e_bwd(nullptr, nullptr, nullptr, 0, 256, 0, nullptr, nullptr, 256,
+                                                         nullptr, nullptr, 0, 2, 0.2f, nullptr, 0, nullptr, 256, nullptr),
+           SIR_OK);
     expect("mask words", (int)sir_mask_words(300, SIR_ACT_LEAKY_RELU), 8);
     expect("mask words (GELU)", (int)sir_mask_words(256, SIR_ACT_GELU), 0);
     // generic path, GraphNorm, plan build

@@ -21,6 +21,9 @@
  *    the edge-materialised helpers (sir_edge_gather_add / _act, sir_segment_*);
  *  - GraphNorm (models/norm.py:7-29): sir_graph_norm_fwd / _bwd, with the stack's activation and
  *    residual fused: sir_graph_norm_act_fwd / _bwd;
+ *  - BatchNorm1d / LayerNorm on node features (models/norm.py:53-60, built by GetNorm, norm.py:68-82) with
+ *    the stack's activation and residual fused: sir_batch_norm_stats / sir_batch_norm_act_fwd / _bwd and
+ *    sir_layer_norm_act_fwd / _bwd;
  *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm.
  *
  * Conventions
@@ -491,6 +494,61 @@ int sir_graph_norm_act_bwd(const int64_t* off, int64_t B, int64_t F, const float
                            const float* dY, int64_t ldg, const float* weight, const float* bias,
                            const float* mean_scale, const float* mean, const float* std_, int act, float slope,
                            float* dX, int64_t lddx, float* dw_part, float* dms_part, float* db_part, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BatchNorm1d and LayerNorm over node features X [M, N] (models/norm.py:53-60; GetNorm 'bn' / 'ln',
+ * norm.py:68-82) with the stack's activation and residual after them, as sir_graph_norm_act_*:
+ *   out = act(y) + R,  act = SIR_ACT_IDENTITY / _RELU / _LEAKY_RELU (slope), R optional (NULL: no add),
+ * torch's own ops (bit-identical to the norm followed by torch's activation and add).  The backward
+ * takes g = act'(y) dY with y recomputed from X by the forward's ops; R's gradient is dY itself (the
+ * caller's).  fp32, any N >= 1: float4 columns when N % 4 == 0 and every row is 16-B aligned (pointers
+ * and leading dimensions), scalar otherwise.  No atomics; every partition of the rows is a function of
+ * (M, N) alone and partials are combined in slab order, so results are run-to-run and device-to-device
+ * bit-identical.  M == 0: no-op.  Added under ABI 17 (new symbols only).
+ *
+ * BatchNorm (N <= 65536): rows in slabs of SIR_BN_SLAB_ROWS; `work` = sir_batch_norm_work_floats(M, N)
+ * floats, 8-B aligned (two [slabs, N] fp64 arrays of per-slab partials + [2, N] fp64), -1 for sizes
+ * out of range.  The [N] statistics mean / invstd are fp64 (double*), as are the sums they come from
+ * (torch's CPU BatchNorm accumulates in fp64 too); per element x - mean and y are formed in fp64 and
+ * rounded to fp32 once, so the error does not grow with |mean| / std (nor with 1 / eps for a two-row batch).
+ *  sir_batch_norm_stats: per column mean = sum x / M, var = sum (x - mean)^2 / M from per-slab
+ *   (count, mean, M2) merged in slab order (Chan), invstd = 1 / sqrt(var + eps) -> mean, invstd [N] fp64.
+ *   running_mean / running_var (both or neither; need M >= 2): updated by the same launch,
+ *   r <- (1 - momentum) r + momentum {mean, var M / (M - 1)}.
+ *  sir_batch_norm_act_fwd: y = (x - mean) invstd weight + bias with the given mean / invstd (training:
+ *   from sir_batch_norm_stats; eval: running_mean, 1 / sqrt(running_var + eps), widened to fp64).
+ *  sir_batch_norm_act_bwd: per slab sum g and dotp = sum g (x - mean), added in slab order:
+ *   dbias = sum g, dweight = dotp invstd; training != 0:
+ *   dX = ((g - dbias / M) - (x - mean) dotp invstd^2 / M) invstd weight; eval: dX = g invstd weight.
+ * ------------------------------------------------------------------------------------------- */
+#define SIR_BN_SLAB_ROWS 128
+int64_t sir_batch_norm_work_floats(int64_t M, int64_t N);
+int sir_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int64_t N, float eps, float momentum,
+                         float* running_mean, float* running_var, double* mean, double* invstd, float* work,
+                         void* stream);
+int sir_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const double* mean, const double* invstd,
+                           const float* weight, const float* bias, int act, float slope, const float* R, int64_t ldr,
+                           float* Y, int64_t ldy, void* stream);
+int sir_batch_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                           const double* mean, const double* invstd, const float* weight, const float* bias, int act,
+                           float slope, int training, float* dX, int64_t lddx, float* dweight, float* dbias,
+                           float* work, void* stream);
+
+/* LayerNorm over the last dimension (N <= 1024), one wave per row: mean, centred (biased) variance,
+ * rstd = 1 / sqrt(var + eps), y = (x - mean) rstd weight + bias; mean / rstd [M] are outputs kept for the
+ * backward.  Backward: dX = rstd (g weight - mean_row(g weight) - xhat mean_row(g weight xhat)) and
+ * P = sir_layer_norm_bwd_parts(M, N) partial rows (-1: sizes out of range) dw_part / db_part [P, ldp] of
+ * dweight = sum g xhat and dbias = sum g (rows [p rpp, (p + 1) rpp), rpp = ceil(M / P)): sum them in
+ * slab order with sir_col_sum. */
+#define SIR_LN_MAX_PARTS 8192
+int64_t sir_layer_norm_bwd_parts(int64_t M, int64_t N);
+int sir_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight, const float* bias,
+                           float eps, int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
+                           float* mean, float* rstd, void* stream);
+int sir_layer_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                           const float* weight, const float* bias, const float* mean, const float* rstd, int act,
+                           float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Device-side graph plan build.  Replaces DGL's lazily built in-edge CSC

@@ -887,6 +887,105 @@ int sir_graph_norm_act_bwd(const int64_t* off, int64_t B, int64_t F, const float
                                               static_cast<hipStream_t>(stream)), nullptr);
 }
 
+// ------------------------------------------------------------------------------ BatchNorm / LayerNorm
+static int check_nodenorm(const char* fn, int64_t M, int64_t N, int64_t n_max, int act) {
+    if (M < 0 || M > ((int64_t)1 << 37)) return fail(SIR_EINVAL, fn, "M out of range");
+    if (N <= 0 || N > n_max) return fail(SIR_EINVAL, fn, n_max == 1024 ? "N must be in [1, 1024]" : "N must be in [1, 65536]");
+    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
+        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
+    return SIR_OK;
+}
+
+int64_t sir_batch_norm_work_floats(int64_t M, int64_t N) {
+    if (M < 0 || M > ((int64_t)1 << 37) || N <= 0 || N > 65536) return -1;
+    return sir::batch_norm_work_floats(M, N);
+}
+
+int sir_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int64_t N, float eps, float momentum,
+                         float* running_mean, float* running_var, double* mean, double* invstd, float* work,
+                         void* stream) {
+    const char* fn = "sir_batch_norm_stats";
+    int rc = check_nodenorm(fn, M, N, 65536, SIR_ACT_IDENTITY);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        return fail(SIR_EINVAL, fn, "running_mean / running_var: both or neither");
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || mean == nullptr || invstd == nullptr || work == nullptr) return fail(SIR_EINVAL, fn, "NULL buffer");
+    if ((reinterpret_cast<uintptr_t>(work) & 7u) != 0) return fail(SIR_EINVAL, fn, "work must be 8-B aligned");
+    if (running_mean != nullptr && M < 2) return fail(SIR_EINVAL, fn, "the running update needs M >= 2");
+    return finish(fn, sir::run_batch_norm_stats(X, ldx, M, (int)N, eps, momentum, running_mean, running_var, mean,
+                                                invstd, work, static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int sir_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const double* mean, const double* invstd,
+                           const float* weight, const float* bias, int act, float slope, const float* R, int64_t ldr,
+                           float* Y, int64_t ldy, void* stream) {
+    const char* fn = "sir_batch_norm_act_fwd";
+    int rc = check_nodenorm(fn, M, N, 65536, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldy < N || (R != nullptr && ldr < N)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr || Y == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_batch_norm_act_fwd(X, ldx, M, (int)N, mean, invstd, weight, bias, act, slope, R, ldr, Y,
+                                                  ldy, static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int sir_batch_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                           const double* mean, const double* invstd, const float* weight, const float* bias, int act,
+                           float slope, int training, float* dX, int64_t lddx, float* dweight, float* dbias,
+                           float* work, void* stream) {
+    const char* fn = "sir_batch_norm_act_bwd";
+    int rc = check_nodenorm(fn, M, N, 65536, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldg < N || lddx < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || dY == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr ||
+        dX == nullptr || dweight == nullptr || dbias == nullptr || work == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    if ((reinterpret_cast<uintptr_t>(work) & 7u) != 0) return fail(SIR_EINVAL, fn, "work must be 8-B aligned");
+    return finish(fn, sir::run_batch_norm_act_bwd(X, ldx, dY, ldg, M, (int)N, mean, invstd, weight, bias, act, slope,
+                                                  training, dX, lddx, dweight, dbias, work,
+                                                  static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int64_t sir_layer_norm_bwd_parts(int64_t M, int64_t N) {
+    if (M < 0 || M > ((int64_t)1 << 37) || N <= 0 || N > 1024) return -1;
+    return sir::layer_norm_parts(M);
+}
+
+int sir_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight, const float* bias,
+                           float eps, int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
+                           float* mean, float* rstd, void* stream) {
+    const char* fn = "sir_layer_norm_act_fwd";
+    int rc = check_nodenorm(fn, M, N, 1024, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldy < N || (R != nullptr && ldr < N)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || weight == nullptr || bias == nullptr || Y == nullptr || mean == nullptr || rstd == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_layer_norm_act_fwd(X, ldx, M, (int)N, weight, bias, eps, act, slope, R, ldr, Y, ldy, mean,
+                                                  rstd, static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int sir_layer_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                           const float* weight, const float* bias, const float* mean, const float* rstd, int act,
+                           float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
+                           void* stream) {
+    const char* fn = "sir_layer_norm_act_bwd";
+    int rc = check_nodenorm(fn, M, N, 1024, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldg < N || lddx < N || ldp < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || dY == nullptr || weight == nullptr || bias == nullptr || mean == nullptr || rstd == nullptr ||
+        dX == nullptr || dw_part == nullptr || db_part == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_layer_norm_act_bwd(X, ldx, dY, ldg, M, (int)N, weight, bias, mean, rstd, act, slope, dX,
+                                                  lddx, dw_part, db_part, ldp, static_cast<hipStream_t>(stream)),
+                  nullptr);
+}
+
 int64_t sir_csr_build_workspace(int64_t n_rows, int64_t E) {
     if (n_rows < 0 || E < 0 || E >= INT32_MAX || n_rows >= INT32_MAX) return -1;
     return sir::csr_build_workspace(n_rows, E);

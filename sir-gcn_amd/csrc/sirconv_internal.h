@@ -100,6 +100,28 @@ hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float*
                               const float* mean, const float* sd, int act, float slope, float* dX, int64_t lddx,
                               float* dw_part, float* dms_part, float* db_part, hipStream_t st);
 
+// BatchNorm1d / LayerNorm with the stack's activation and residual (sirconv_nodenorm.hip)
+int64_t batch_norm_slabs(int64_t M);
+int64_t batch_norm_work_floats(int64_t M, int64_t N);
+hipError_t run_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int N, float eps, float momentum,
+                                float* run_mean, float* run_var, double* mean, double* invstd, float* work,
+                                hipStream_t st);
+hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
+                                  const double* invstd, const float* gamma, const float* beta, int act, float slope,
+                                  const float* R, int64_t ldr, float* Y, int64_t ldy, hipStream_t st);
+hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                  const double* mean, const double* invstd, const float* gamma, const float* beta,
+                                  int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
+                                  float* dbeta, float* work, hipStream_t st);
+int64_t layer_norm_parts(int64_t M);
+hipError_t run_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
+                                  const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
+                                  float* Y, int64_t ldy, float* mean, float* rstd, hipStream_t st);
+hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                  const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                  int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
+                                  int64_t ldp, hipStream_t st);
+
 hipError_t run_degree_norms(const int* rowptr_a, float* norm_a, const int* rowptr_b, float* norm_b,
                             int64_t n, hipStream_t st);
 

@@ -39,6 +39,16 @@ SIGNATURES = {
                                               _P, _P, _P]),
     "sir_graph_norm_act_bwd": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I, _F, _P,
                                               _I64, _P, _P, _P, _P]),
+    "sir_batch_norm_work_floats": (ctypes.c_int64, [_I64, _I64]),
+    "sir_batch_norm_stats": (ctypes.c_int, [_P, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "sir_batch_norm_act_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _P, _I64, _P]),
+    "sir_batch_norm_act_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _I, _P, _I64,
+                                              _P, _P, _P, _P]),
+    "sir_layer_norm_bwd_parts": (ctypes.c_int64, [_I64, _I64]),
+    "sir_layer_norm_act_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _F, _I, _F, _P, _I64, _P, _I64, _P, _P,
+                                              _P]),
+    "sir_layer_norm_act_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _P,
+                                              _P, _I64, _P]),
     "sir_edge_gather_add": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "sir_edge_gather_act": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _F, _P, _I64, _P, _P]),
     "sir_segment_sum": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _I, _P, _I64,
@@ -544,6 +554,83 @@ def graph_norm_bwd(off, X, dY, weight, mean_scale, mean, std, dX, dw_part, dms_p
                                     _ptr(mean_scale), _ptr(mean), _ptr(std), _ptr(dX), _ld(dX, F),
                                     _ptr(dw_part), _ptr(dms_part), _ptr(db_part), _stream(dX.device))
     _check(rc, lib)
+
+
+# ------------------------------------------------------------------------------ BatchNorm / LayerNorm
+BN_SLAB_ROWS = 128        # SIR_BN_SLAB_ROWS
+
+
+def batch_norm_work(M, N, device):
+    """The fp32 workspace of :func:`batch_norm_stats` / :func:`batch_norm_act_bwd` for an [M, N] input."""
+    n = int(load().sir_batch_norm_work_floats(M, N))
+    if n < 0:
+        raise RuntimeError(f"sir_batch_norm_work_floats({M}, {N}): sizes out of range")
+    return torch.empty((max(n, 1),), device=device, dtype=torch.float32)
+
+
+def batch_norm_stats(X, eps, momentum, running_mean, running_var, mean, invstd, work):
+    """Per-column mean / invstd of X [M, N] (``sir_batch_norm_stats``); the running buffers, when given,
+    are updated by the same launch."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_batch_norm_stats", X.device):
+        rc = lib.sir_batch_norm_stats(_ptr(X), _ld(X, N), M, N, float(eps), float(momentum), _ptr(running_mean),
+                                      _ptr(running_var), _ptr(mean), _ptr(invstd), _ptr(work), _stream(X.device))
+    _check(rc, lib)
+
+
+def batch_norm_act_fwd(X, mean, invstd, weight, bias, act, slope, R, Y):
+    """Y = act((X - mean) invstd weight + bias) + R in one pass (``sir_batch_norm_act_fwd``; R may be None)."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_batch_norm_act_fwd", X.device):
+        rc = lib.sir_batch_norm_act_fwd(_ptr(X), _ld(X, N), M, N, _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias),
+                                        int(act), float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y),
+                                        _ld(Y, N), _stream(X.device))
+    _check(rc, lib)
+
+
+def batch_norm_act_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, dX, dweight, dbias, work):
+    """Backward of :func:`batch_norm_act_fwd` (``sir_batch_norm_act_bwd``): dX, dweight, dbias."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_batch_norm_act_bwd", X.device):
+        rc = lib.sir_batch_norm_act_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(mean), _ptr(invstd),
+                                        _ptr(weight), _ptr(bias), int(act), float(slope), int(bool(training)),
+                                        _ptr(dX), _ld(dX, N), _ptr(dweight), _ptr(dbias), _ptr(work),
+                                        _stream(X.device))
+    _check(rc, lib)
+
+
+def layer_norm_act_fwd(X, weight, bias, eps, act, slope, R, Y, mean, rstd):
+    """Y = act(LayerNorm(X)) + R in one pass (``sir_layer_norm_act_fwd``); mean / rstd [M] for the backward."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_layer_norm_act_fwd", X.device):
+        rc = lib.sir_layer_norm_act_fwd(_ptr(X), _ld(X, N), M, N, _ptr(weight), _ptr(bias), float(eps), int(act),
+                                        float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y), _ld(Y, N),
+                                        _ptr(mean), _ptr(rstd), _stream(X.device))
+    _check(rc, lib)
+
+
+def layer_norm_act_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX):
+    """Backward of :func:`layer_norm_act_fwd`: writes dX, returns (dweight, dbias) — the per-slab partial
+    rows of ``sir_layer_norm_act_bwd`` summed in slab order by ``sir_col_sum``."""
+    lib = load()
+    M, N = X.shape
+    parts = int(lib.sir_layer_norm_bwd_parts(M, N))
+    if parts < 0:
+        raise RuntimeError(f"sir_layer_norm_bwd_parts({M}, {N}): sizes out of range")
+    npad = (N + 3) // 4 * 4
+    part = torch.empty((max(parts, 1), 2 * npad), device=X.device, dtype=torch.float32)
+    db_part = part[:, npad:]
+    with _Timed("sir_layer_norm_act_bwd", X.device):
+        rc = lib.sir_layer_norm_act_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(weight), _ptr(bias),
+                                        _ptr(mean), _ptr(rstd), int(act), float(slope), _ptr(dX), _ld(dX, N),
+                                        _ptr(part), _ptr(db_part), 2 * npad, _stream(X.device))
+    _check(rc, lib)
+    tot = col_sum(part[:parts])             # (the pad columns of an N % 4 != 0 row are summed and dropped)
+    return tot[:N], tot[npad:npad + N]
 
 
 # ------------------------------------------------------------------------------ projection GEMMs

@@ -1,4 +1,11 @@
-"""Fused GraphNorm on MI355X — drop-in for the reference ``models/norm.py:7-29`` ``GraphNorm``.
+"""Native norms on MI355X: GraphNorm, and BatchNorm1d / LayerNorm over node features.
+
+``GraphBatchNorm`` / ``GraphLayerNorm`` / ``GetNorm`` are drop-ins for ``models/norm.py:53-60,68-82``:
+torch's own constructors and ``state_dict`` keys, ``forward(graphs, feats)`` or ``forward(feats)``, and
+``forward_act(graphs, feats, activation, resid)`` = ``activation(norm(feats)) + resid`` in one pass per
+direction (``sir_batch_norm_*`` / ``sir_layer_norm_*``), which ``SIRStack`` picks up.
+
+Fused GraphNorm on MI355X — drop-in for the reference ``models/norm.py:7-29`` ``GraphNorm``.
 
 Same constructor ``GraphNorm(normalized_shape, eps=1e-05, bias=True, mean_scale=True)``, same
 parameters (``weight``, ``bias`` (or the int 0), ``mean_scale`` (or the int 1)) and
@@ -102,6 +109,12 @@ def _act_code(m):
     return None
 
 
+def _hooked(*modules):
+    """True when a hook waits on the call of any of ``modules`` (a fused pass would skip it)."""
+    return any(len(h) for m in modules for h in (m._forward_pre_hooks, m._forward_hooks,
+                                                 m._backward_hooks, m._backward_pre_hooks))
+
+
 class GraphNorm(nn.Module):
     """``models/norm.py:7-29`` GraphNorm, fused (see module docstring)."""
 
@@ -125,8 +138,7 @@ class GraphNorm(nn.Module):
         direction, or None when the activation / operands are not the fused kernel's, or a hook
         waits on either module's call (the caller then runs the three steps itself)."""
         code = _act_code(activation)
-        hooked = any(len(h) for m in (self, activation) for h in (m._forward_pre_hooks, m._forward_hooks,
-                                                                 m._backward_hooks, m._backward_pre_hooks))
+        hooked = _hooked(self, activation)
         if (code is None or hooked or feats.dim() != 2 or not feats.is_cuda
                 or (resid is not None and (resid.dtype != torch.float32 or resid.shape != feats.shape))):
             return None
@@ -134,3 +146,186 @@ class GraphNorm(nn.Module):
         b = self.bias if isinstance(self.bias, torch.Tensor) else None
         ms = self.mean_scale if isinstance(self.mean_scale, torch.Tensor) else None
         return GraphNormActFunction.apply(feats, self.weight, b, ms, off, float(self.eps), code[0], code[1], resid)
+
+
+def _rows(t, N):
+    """``t`` [M, N] with unit-stride rows at least N apart (a column slice of a wider tensor stays a view)."""
+    return t if t.stride(1) == 1 and t.stride(0) >= N else t.contiguous()
+
+
+class BatchNormActFunction(torch.autograd.Function):
+    """act(BatchNorm1d(X)) + R: ``sir_batch_norm_stats`` (training: the batch statistics and the running
+    buffers' update in one launch) and one apply pass; the backward is a reduce pass and an apply pass.
+    Saves X and the [N] statistics only — y is recomputed; R's gradient is the incoming gradient itself."""
+
+    @staticmethod
+    def forward(ctx, X, weight, bias, running_mean, running_var, training, momentum, eps, act, slope, R):
+        M, N = X.shape
+        X = _rows(X, N)
+        w, b = weight.contiguous(), bias.contiguous()
+        Y = torch.empty((M, N), device=X.device, dtype=torch.float32)
+        if training:
+            mean = torch.empty((N,), device=X.device, dtype=torch.float64)     # the [N] statistics are fp64
+            invstd = torch.empty_like(mean)
+            if M > 0:
+                _native.batch_norm_stats(X, eps, momentum, running_mean, running_var, mean, invstd,
+                                         _native.batch_norm_work(M, N, X.device))
+        else:
+            mean, invstd = running_mean.double(), torch.rsqrt(running_var.double() + eps)
+        if M > 0:
+            _native.batch_norm_act_fwd(X, mean, invstd, w, b, act, slope, _rows(R, N) if R is not None else None, Y)
+        ctx.save_for_backward(X, w, b, mean, invstd)
+        ctx.cfg = (bool(training), act, slope, R is not None)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, w, b, mean, invstd = ctx.saved_tensors
+        training, act, slope, has_r = ctx.cfg
+        M, N = X.shape
+        dY = _rows(dY.float(), N)
+        dX = torch.empty((M, N), device=X.device, dtype=torch.float32)
+        if M > 0:
+            dw = torch.empty((N,), device=X.device, dtype=torch.float32)
+            db = torch.empty_like(dw)
+            _native.batch_norm_act_bwd(X, dY, mean, invstd, w, b, act, slope, training, dX, dw, db,
+                                       _native.batch_norm_work(M, N, X.device))
+        else:
+            dw = torch.zeros((N,), device=X.device, dtype=torch.float32)
+            db = torch.zeros_like(dw)
+        return dX, dw, db, None, None, None, None, None, None, None, dY if has_r else None
+
+
+class LayerNormActFunction(torch.autograd.Function):
+    """act(LayerNorm(X)) + R in one pass per direction (``sir_layer_norm_act_fwd`` / ``_bwd``).  Saves X and
+    the [M] mean / rstd only; R's gradient is the incoming gradient itself."""
+
+    @staticmethod
+    def forward(ctx, X, weight, bias, eps, act, slope, R):
+        M, N = X.shape
+        X = _rows(X, N)
+        w, b = weight.contiguous(), bias.contiguous()
+        Y = torch.empty((M, N), device=X.device, dtype=torch.float32)
+        mean = torch.empty((M,), device=X.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        if M > 0:
+            _native.layer_norm_act_fwd(X, w, b, eps, act, slope, _rows(R, N) if R is not None else None, Y, mean, rstd)
+        ctx.save_for_backward(X, w, b, mean, rstd)
+        ctx.cfg = (act, slope, R is not None)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, w, b, mean, rstd = ctx.saved_tensors
+        act, slope, has_r = ctx.cfg
+        M, N = X.shape
+        dY = _rows(dY.float(), N)
+        dX = torch.empty((M, N), device=X.device, dtype=torch.float32)
+        dw, db = _native.layer_norm_act_bwd(X, dY, w, b, mean, rstd, act, slope, dX)
+        return dX, dw, db, None, None, None, dY if has_r else None
+
+
+def _fusable(norm, activation, feats, resid):
+    """(code, slope) when ``forward_act`` may run the fused pass on these operands, else None."""
+    code = _act_code(activation)
+    if (code is None or _hooked(norm, activation) or not feats.is_cuda or not norm._native_ok(feats)
+            or (resid is not None and (resid.dtype != torch.float32 or resid.shape != feats.shape
+                                       or resid.device != feats.device))):
+        return None
+    return code
+
+
+class GraphBatchNorm(nn.BatchNorm1d):
+    """``models/norm.py:53-55`` GraphBatchNorm / ``nn.BatchNorm1d``: torch's constructor and state_dict;
+    ``forward(graphs, feats)`` or ``forward(feats)``.  A CUDA fp32 [M, N] input on the default-configured
+    module (affine, tracked running statistics, a float momentum) runs the native kernels; every other
+    configuration or input type runs torch's own forward.  No CPU fallback."""
+
+    def _native_ok(self, feats):
+        return (feats.dim() == 2 and feats.dtype == torch.float32 and self.affine and self.track_running_stats
+                and self.momentum is not None and self.weight.dtype == torch.float32
+                and feats.shape[1] == self.num_features)
+
+    def _run(self, feats, code, resid):
+        if self.training:
+            if feats.shape[0] == 1:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {feats.size()}")
+            self.num_batches_tracked.add_(1)            # a device op: no host synchronisation
+        return BatchNormActFunction.apply(feats, self.weight, self.bias, self.running_mean, self.running_var,
+                                          self.training, float(self.momentum), float(self.eps), code[0], code[1],
+                                          resid)
+
+    def forward(self, *args):
+        feats = args[-1]
+        if not feats.is_cuda:
+            raise RuntimeError("sirgcn.GraphBatchNorm needs a ROCm GPU tensor (no CPU fallback)")
+        if not self._native_ok(feats):
+            return super().forward(feats)
+        return self._run(feats, (_native.ACT_IDENTITY, 0.0), None)
+
+    def forward_act(self, graphs, feats, activation, resid=None):
+        """``activation(self(graphs, feats)) + resid`` (resid None: no add) in one pass per direction, or
+        None when the activation / operands are not the fused kernel's, or a hook waits on either
+        module's call (the caller then runs the three steps itself)."""
+        code = _fusable(self, activation, feats, resid)
+        return None if code is None else self._run(feats, code, resid)
+
+
+class GraphLayerNorm(nn.LayerNorm):
+    """``models/norm.py:58-60`` GraphLayerNorm / ``nn.LayerNorm`` over the feature dimension: as
+    :class:`GraphBatchNorm`; native for an elementwise-affine module with N <= 1024."""
+
+    def _native_ok(self, feats):
+        return (feats.dim() == 2 and feats.dtype == torch.float32 and self.elementwise_affine
+                and self.weight is not None and self.bias is not None and self.weight.dtype == torch.float32
+                and len(self.normalized_shape) == 1 and feats.shape[1] == self.normalized_shape[0] <= 1024)
+
+    def _run(self, feats, code, resid):
+        return LayerNormActFunction.apply(feats, self.weight, self.bias, float(self.eps), code[0], code[1], resid)
+
+    def forward(self, *args):
+        feats = args[-1]
+        if not feats.is_cuda:
+            raise RuntimeError("sirgcn.GraphLayerNorm needs a ROCm GPU tensor (no CPU fallback)")
+        if not self._native_ok(feats):
+            return super().forward(feats)
+        return self._run(feats, (_native.ACT_IDENTITY, 0.0), None)
+
+    def forward_act(self, graphs, feats, activation, resid=None):
+        """As :meth:`GraphBatchNorm.forward_act`."""
+        code = _fusable(self, activation, feats, resid)
+        return None if code is None else self._run(feats, code, resid)
+
+
+class GraphIdentity(nn.Identity):
+    """``models/norm.py:63-65``: no norm, called as ``(graphs, feats)`` or ``(feats)``."""
+
+    def forward(self, *args):
+        return args[-1]
+
+
+class GetNorm(nn.Module):
+    """``models/norm.py:68-82``: the norm named 'gn' (GraphNorm, ``with_graph`` only), 'bn', 'ln' or 'none' as
+    ``self.norm`` (so the reference's ``norm.*`` state_dict keys), called as ``(graphs, feats)`` when
+    ``with_graph`` else ``(feats)``.  'cn' (ContraNorm) is not built."""
+
+    def __init__(self, norm, with_graph, *args, **kwargs):
+        super().__init__()
+        norm_list = {"bn": GraphBatchNorm, "ln": GraphLayerNorm, "none": GraphIdentity}
+        if with_graph:
+            norm_list["gn"] = GraphNorm
+        if norm == "cn":
+            raise NotImplementedError("norm = cn (ContraNorm) is not built by sirgcn")
+        if norm not in norm_list:
+            raise NotImplementedError(f"norm = {norm} not implemented")
+        self.norm = norm_list[norm](*args, **kwargs)
+
+    def forward(self, *args):
+        return self.norm(*args)
+
+    def forward_act(self, graphs, feats, activation, resid=None):
+        """The inner norm's fused ``forward_act`` when it has one and no hook waits on this wrapper."""
+        fuse = getattr(self.norm, "forward_act", None)
+        if fuse is None or _hooked(self):
+            return None
+        return fuse(graphs, feats, activation, resid)

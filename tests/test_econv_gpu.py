@@ -12,6 +12,7 @@ from torch import nn
 
 import oracle
 from conftest import assert_close, assert_parity
+from exact_cases import encode_mask as _encode_mask
 
 from sirgcn import SIREConv, _native
 from sirgcn.conv import edge_backward
@@ -121,24 +122,6 @@ def _legacy_S(plan, Q, K, Eh, agg, act):
     n = max(plan.dst.n_slots, 1)
     _native.segment_sum(plan.dst, A, S, in_norm, out_norm, agg == "mean", partial=torch.empty((n * H,), device=DEV))
     return S
-
-
-def _encode_mask(zpos, H):
-    """The documented sir_mask_words layout of the boolean [E, H] array ``zpos`` (bits past H zero)."""
-    E = zpos.shape[0]
-    if H > 128:
-        nw = 4 * ((H + 255) // 256)
-        bit = lambda f: (4 * ((f // 4) // 64) + f % 4, (f // 4) % 64)
-    else:
-        hc = H // 4
-        L = 4 if hc <= 4 else 8 if hc <= 8 else 16 if hc <= 16 else 32
-        nw = max(L // 16, 1)
-        bit = lambda f: divmod((f % 4) * L + f // 4, 64)[0:2]
-    out = np.zeros((E, nw), dtype=np.uint64)
-    for f in range(H):
-        w, b = bit(f)
-        out[:, w] |= zpos[:, f].astype(np.uint64) << np.uint64(b)
-    return out
 
 
 @pytest.mark.parametrize("chunk", [64, 256])

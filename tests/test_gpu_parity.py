@@ -673,16 +673,29 @@ def test_native_plan_build_batched_molecules_speed():
     assert ts["native"] <= ts["torch"] * 1.5
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 @pytest.mark.parametrize("agg", ["sum", "sym", "mean"])
 @pytest.mark.parametrize("chunk", [256, 4])
 def test_one_launch_backward_bit_identical_to_two_passes(agg, dtype, chunk):
+    _one_launch_vs_two_passes(agg, dtype, chunk, 256)
+
+
+@pytest.mark.parametrize("H", [76, 128, 512])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("agg", ["sum", "sym", "mean"])
+@pytest.mark.parametrize("chunk", [256, 4])
+def test_one_launch_backward_bit_identical_to_two_passes_other_widths(agg, dtype, chunk, H):
+    _one_launch_vs_two_passes(agg, dtype, chunk, H)
+
+
+def _one_launch_vs_two_passes(agg, dtype, chunk, H):
     """sir_edge_agg_bwd (dQ pass || dK pass in one launch; MEAN on G / deg formed first) ==
     sir_edge_agg_bwd_dst + _src (MEAN: the dst pass divides and writes G / deg for the src pass),
-    bit for bit."""
+    bit for bit — fp32 and both 16-bit storages, at a sub-wave width (76), 128, and one, two full-wave
+    passes (256, 512; the widths beside 256 on a smaller graph)."""
     from sirgcn.conv import edge_backward
     gen = torch.Generator().manual_seed(21)
-    V, E, H = 3000, 60000, 256
+    V, E = (3000, 60000) if H == 256 else (1500, 24000)
     src = torch.randint(0, V, (E,), generator=gen)
     dst = torch.randint(0, V, (E,), generator=gen)
     dst[:3000] = 17                                       # hub rows: split items on both plans
@@ -693,7 +706,7 @@ def test_one_launch_backward_bit_identical_to_two_passes(agg, dtype, chunk):
     G = torch.randn(V, H, generator=gen).to(DEV, dtype)
     in_norm, out_norm = plan.norms(agg)
     S = torch.empty(V, H, device=DEV, dtype=dtype)
-    mask = torch.empty(E * 4, device=DEV, dtype=torch.int64)
+    mask = torch.empty(E * _native.mask_words(H, _native.ACT_LEAKY), device=DEV, dtype=torch.int64)
     part = torch.empty(max(plan.dst.n_slots, plan.src.n_slots) * H, device=DEV)
     _native.edge_agg_fwd(plan.dst, QK[:, :H], QK[:, H:], in_norm, out_norm, agg, _native.ACT_LEAKY, 0.2, S, part, mask)
     outs = []
@@ -710,10 +723,27 @@ def test_one_launch_backward_bit_identical_to_two_passes(agg, dtype, chunk):
     assert torch.isfinite(outs[0]).all()
 
 
-@pytest.mark.parametrize("H", [4, 12, 32, 60, 64, 76, 80, 96, 128, 136, 256, 512, 776, 1024])
+SIGN_MASK_WIDTHS = [4, 12, 32, 60, 64, 76, 80, 96, 128, 136, 256, 512, 776, 1024]
+
+
+@pytest.mark.parametrize("H", SIGN_MASK_WIDTHS)
 @pytest.mark.parametrize("agg", ["sum", "mean", "sym"])
 @pytest.mark.parametrize("act", ["relu", "leaky"])
 def test_sign_mask_backward_bit_identical_all_widths(H, agg, act):
+    _sign_mask_vs_recompute(H, agg, act, torch.float32)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("H", SIGN_MASK_WIDTHS)
+@pytest.mark.parametrize("agg", ["sum", "mean", "sym"])
+@pytest.mark.parametrize("act", ["relu", "leaky"])
+def test_sign_mask_backward_bit_identical_all_widths_16bit(H, agg, act, dtype):
+    """The bf16 / fp16 compile units of the same passes (all widths are multiples of 4, as 16-bit storage
+    requires): Q, K, G cast to the storage type before the call."""
+    _sign_mask_vs_recompute(H, agg, act, dtype)
+
+
+def _sign_mask_vs_recompute(H, agg, act, dtype):
     """Sign-mask backward == the recompute backward, bit for bit, at every mask layout: full-wave
     rows (wide-chunk dQ pass, every word count per edge, H = 136 .. 1024) and sub-wave rows (H <= 128:
     4 / 8 / 16 / 32 lanes per row, the reference's published widths 60, 76 = 75 padded, 80, 96 = 95
@@ -726,16 +756,16 @@ def test_sign_mask_backward_bit_identical_all_widths(H, agg, act):
     dst[:300] = 11                                        # a hub row (split at chunk 64)
     plan = GraphPlan(src, dst, V, DEV, chunk=64)
     code = _native.ACT_RELU if act == "relu" else _native.ACT_LEAKY
-    QK = torch.randn(V, 2 * H, generator=gen).to(DEV)
-    G = torch.randn(V, H, generator=gen).to(DEV)
+    QK = torch.randn(V, 2 * H, generator=gen).to(DEV, dtype)
+    G = torch.randn(V, H, generator=gen).to(DEV, dtype)
     in_norm, out_norm = plan.norms(agg)
-    S = torch.empty(V, H, device=DEV)
+    S = torch.empty(V, H, device=DEV, dtype=dtype)
     mask = torch.empty(E * _native.mask_words(H, code), device=DEV, dtype=torch.int64)
     part = torch.empty(max(plan.dst.n_slots, plan.src.n_slots, 1) * H, device=DEV)
     _native.edge_agg_fwd(plan.dst, QK[:, :H], QK[:, H:], in_norm, out_norm, agg, code, 0.2, S, part, mask)
     outs = []
     for m in (mask, None):
-        dQK = torch.full((V, 2 * H), float("nan"), device=DEV)
+        dQK = torch.full((V, 2 * H), float("nan"), device=DEV, dtype=dtype)
         edge_backward(plan, H, agg, code, 0.2, G, QK[:, :H], QK[:, H:], m, dQK)
         outs.append(dQK)
     torch.cuda.synchronize()

@@ -24,6 +24,8 @@
  *  - BatchNorm1d / LayerNorm on node features (models/norm.py:53-60, built by GetNorm, norm.py:68-82) with
  *    the stack's activation and residual fused: sir_batch_norm_stats / sir_batch_norm_act_fwd / _bwd and
  *    sir_layer_norm_act_fwd / _bwd;
+ *  - the graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling, dgl.broadcast_nodes; ogbg-molhiv/model.py:69,85,
+ *    zinc/model.py:41): sir_graph_pool_fwd / _bwd (sir_graph_pool_work_floats, sir_graph_pool_slab_rows);
  *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm.
  *
  * Conventions
@@ -549,6 +551,45 @@ int sir_layer_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t
                            const float* weight, const float* bias, const float* mean, const float* rstd, int act,
                            float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling: ogbg-molhiv/model.py:69,85, zinc/model.py:41,
+ * super-pixel/model.py:28, hetero-edge-count/model.py:23,33; dgl.broadcast_nodes is the backward of SUM) on
+ * a batched graph: graph b owns node rows [off[b], off[b+1]) of X [V, F] (off = int64 [B+1], off[B] = V, as
+ * for GraphNorm).  Added under ABI 17 (new symbols only).
+ *   forward : P[b, c] = reduce over the graph's rows of X[v, c], op = SIR_POOL_SUM / _MEAN / _MAX
+ *     SUM : fp32 sum in node order.
+ *     MEAN: that sum, IEEE-divided by (float)max(n_b, 1) (DGL's segment_reduce('mean') clamp).
+ *     MAX : starts from the first row and takes a later row only on a strict >, so the lowest node id wins a
+ *           tie; arg[b, c] (int32 [B, F], required for MAX, not touched otherwise) is the winning row
+ *           relative to off[b].
+ *     An empty graph gives P = 0 and arg = -1 (DGL's zero fill of empty segments).
+ *   backward: dX [V, F], fully written:
+ *     SUM : dX[v] = dP[b(v)];   MEAN: dX[v] = dP[b(v)] / (float)n_b (IEEE division);
+ *     MAX : dX[v, c] = arg[b, c] == v - off[b] ? dP[b, c] : 0.
+ * X, P, dP, dX are in `dtype` (SIR_DTYPE_F32 / BF16 / F16); sums, the division and the comparison run in
+ * fp32 and each output is rounded once.  Inputs that contain NaN or +-inf are not specified.
+ * Any 1 <= F <= 65536, any leading dimension >= F: 4-element (16-B / 8-B) column accesses when F % 4 == 0,
+ * the leading dimensions are multiples of 4 and the pointers are aligned to 4 elements (arg to 16 B),
+ * scalar accesses otherwise.
+ * Partition (no atomics, no host read of `off`, graph-capturable): a graph is cut into slabs of
+ * sir_graph_pool_slab_rows() = SIR_POOL_SLAB_ROWS rows counted from its own first row; graph b owns the
+ * slab slots [b + off[b] / R, b + 1 + off[b+1] / R), B + V / R in all, one wave per (slot, 64-lane column
+ * chunk).  A graph of at most R rows is reduced in node order by its one wave; a longer graph's slab
+ * partials (value, and arg for MAX) go to `work` and are combined in slab order by a second launch
+ * (issued when V > R).  The partition is a function of (off, F) alone: bit-identical run to run.
+ * work: sir_graph_pool_work_floats(V, B, F, op) floats (0 when V <= R or B == 0; -1 on arguments out of
+ * range), required when that is > 0; the backward needs none.
+ * B == 0: no-op (NULL buffers accepted).  V == 0 with B > 0: P = 0, arg = -1 (X may be NULL).
+ * ------------------------------------------------------------------------------------------- */
+enum { SIR_POOL_SUM = 0, SIR_POOL_MEAN = 1, SIR_POOL_MAX = 2 };
+#define SIR_POOL_SLAB_ROWS 1024
+int64_t sir_graph_pool_slab_rows(void);
+int64_t sir_graph_pool_work_floats(int64_t V, int64_t B, int64_t F, int op);
+int sir_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int op, int dtype,
+                       const void* X, int64_t ldx, void* P, int64_t ldp, int32_t* arg, float* work, void* stream);
+int sir_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int op, int dtype,
+                       const void* dP, int64_t ldg, const int32_t* arg, void* dX, int64_t lddx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Device-side graph plan build.  Replaces DGL's lazily built in-edge CSC

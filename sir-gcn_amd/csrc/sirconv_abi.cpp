@@ -986,6 +986,55 @@ int sir_layer_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t
                   nullptr);
 }
 
+// ------------------------------------------------------------------------------ graph readout
+static int check_pool(const char* fn, int64_t B, int64_t V, int64_t F, int op, int dtype, int64_t ld_a, int64_t ld_b) {
+    if (F <= 0 || F > 65536) return fail(SIR_EINVAL, fn, "F must be in [1, 65536]");
+    if (B < 0 || V < 0 || B > ((int64_t)1 << 37) || V > ((int64_t)1 << 37))
+        return fail(SIR_EINVAL, fn, "B and V must be in [0, 2^37]");
+    if (ld_a < F || ld_b < F) return fail(SIR_EINVAL, fn, "leading dimensions must be >= F");
+    if (op != SIR_POOL_SUM && op != SIR_POOL_MEAN && op != SIR_POOL_MAX)
+        return fail(SIR_EINVAL, fn, "op must be SIR_POOL_SUM, _MEAN or _MAX");
+    if (dtype != SIR_DTYPE_F32 && dtype != SIR_DTYPE_BF16 && dtype != SIR_DTYPE_F16)
+        return fail(SIR_EINVAL, fn, "dtype must be SIR_DTYPE_F32, _BF16 or _F16");
+    return SIR_OK;
+}
+
+int64_t sir_graph_pool_slab_rows(void) { return SIR_POOL_SLAB_ROWS; }
+
+int64_t sir_graph_pool_work_floats(int64_t V, int64_t B, int64_t F, int op) {
+    if (V < 0 || B < 0 || V > ((int64_t)1 << 37) || B > ((int64_t)1 << 37) || F <= 0 || F > 65536) return -1;
+    if (op != SIR_POOL_SUM && op != SIR_POOL_MEAN && op != SIR_POOL_MAX) return -1;
+    return sir::graph_pool_work_floats(V, B, F, op);
+}
+
+int sir_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int op, int dtype,
+                       const void* X, int64_t ldx, void* P, int64_t ldp, int32_t* arg, float* work, void* stream) {
+    const char* fn = "sir_graph_pool_fwd";
+    int rc = check_pool(fn, B, V, F, op, dtype, ldx, ldp);
+    if (rc != SIR_OK) return rc;
+    if (B == 0) return SIR_OK;
+    if (off == nullptr || P == nullptr || (V > 0 && X == nullptr)) return fail(SIR_EINVAL, fn, "NULL buffer");
+    if (op == SIR_POOL_MAX && arg == nullptr) return fail(SIR_EINVAL, fn, "MAX needs arg");
+    if (work == nullptr && sir::graph_pool_work_floats(V, B, F, op) > 0)
+        return fail(SIR_EINVAL, fn, "work needed (sir_graph_pool_work_floats)");
+    return finish(fn, sir::run_graph_pool_fwd(off, B, V, (int)F, op, dtype, X, ldx, P, ldp,
+                                              op == SIR_POOL_MAX ? arg : nullptr, work,
+                                              static_cast<hipStream_t>(stream)), "too many slab slots for one launch");
+}
+
+int sir_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int op, int dtype,
+                       const void* dP, int64_t ldg, const int32_t* arg, void* dX, int64_t lddx, void* stream) {
+    const char* fn = "sir_graph_pool_bwd";
+    int rc = check_pool(fn, B, V, F, op, dtype, ldg, lddx);
+    if (rc != SIR_OK) return rc;
+    if (B == 0) return SIR_OK;
+    if (off == nullptr || dP == nullptr || (V > 0 && dX == nullptr)) return fail(SIR_EINVAL, fn, "NULL buffer");
+    if (op == SIR_POOL_MAX && arg == nullptr) return fail(SIR_EINVAL, fn, "MAX needs arg");
+    return finish(fn, sir::run_graph_pool_bwd(off, B, V, (int)F, op, dtype, dP, ldg,
+                                              op == SIR_POOL_MAX ? arg : nullptr, dX, lddx,
+                                              static_cast<hipStream_t>(stream)), "too many slab slots for one launch");
+}
+
 int64_t sir_csr_build_workspace(int64_t n_rows, int64_t E) {
     if (n_rows < 0 || E < 0 || E >= INT32_MAX || n_rows >= INT32_MAX) return -1;
     return sir::csr_build_workspace(n_rows, E);

@@ -122,6 +122,14 @@ hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, i
                                   int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
                                   int64_t ldp, hipStream_t st);
 
+// graph readout: sum / mean / max pooling over the graphs of a batch and its backward (sirconv_readout.hip)
+int64_t graph_pool_slots(int64_t V, int64_t B);
+int64_t graph_pool_work_floats(int64_t V, int64_t B, int64_t F, int op);
+hipError_t run_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int F, int op, int dtype, const void* X,
+                              int64_t ldx, void* P, int64_t ldp, int* arg, float* work, hipStream_t st);
+hipError_t run_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int F, int op, int dtype, const void* dP,
+                              int64_t ldg, const int* arg, void* dX, int64_t lddx, hipStream_t st);
+
 hipError_t run_degree_norms(const int* rowptr_a, float* norm_a, const int* rowptr_b, float* norm_b,
                             int64_t n, hipStream_t st);
 

@@ -49,6 +49,10 @@ SIGNATURES = {
                                               _P]),
     "sir_layer_norm_act_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _P,
                                               _P, _I64, _P]),
+    "sir_graph_pool_slab_rows": (ctypes.c_int64, []),
+    "sir_graph_pool_work_floats": (ctypes.c_int64, [_I64, _I64, _I64, _I]),
+    "sir_graph_pool_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _I64, _P, _P, _P]),
+    "sir_graph_pool_bwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _P, _I64, _P]),
     "sir_edge_gather_add": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "sir_edge_gather_act": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _F, _P, _I64, _P, _P]),
     "sir_segment_sum": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _I, _P, _I64,
@@ -600,6 +604,73 @@ def batch_norm_act_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, 
                                         _ptr(dX), _ld(dX, N), _ptr(dweight), _ptr(dbias), _ptr(work),
                                         _stream(X.device))
     _check(rc, lib)
+
+
+# ------------------------------------------------------------------------------ graph readout
+POOL_SUM, POOL_MEAN, POOL_MAX = 0, 1, 2     # SIR_POOL_*
+POOL_SLAB_ROWS = 1024                       # SIR_POOL_SLAB_ROWS
+
+
+def graph_pool_work(V, B, F, op, device):
+    """The fp32 workspace of :func:`graph_pool_fwd` (slab partials of graphs longer than one slab), or None."""
+    if V <= POOL_SLAB_ROWS or B == 0:           # sir_graph_pool_work_floats is 0 there: no graph can be longer
+        return None
+    n = int(load().sir_graph_pool_work_floats(V, B, F, int(op)))
+    if n < 0:
+        raise RuntimeError(f"sir_graph_pool_work_floats({V}, {B}, {F}, {op}): arguments out of range")
+    return torch.empty((n,), device=device, dtype=torch.float32) if n > 0 else None
+
+
+# The readout is one small launch per direction on launch-bound batches (64 molecules: a few us of GPU
+# work), so its two bindings keep the host path short: raw data pointers (ctypes takes an int for a
+# void*), the raw stream handle, and the event pair only while timing is on.
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def _stream_of(device):
+    if _raw_stream is not None and device.index is not None:
+        return _raw_stream(device.index)
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def graph_pool_fwd(off, X, op, P, arg=None):
+    """P [B, F] = sum / mean / max of X [V, F] over the graphs' rows (``sir_graph_pool_fwd``); arg int32
+    [B, F] for max.  X and P share one of fp32 / bf16 / fp16; rows are unit-stride."""
+    lib = _lib if _lib is not None else load()
+    V = X.shape[0]
+    B, F = P.shape
+    if X.dtype is not P.dtype or X.stride(1) != 1 or P.stride(1) != 1:
+        raise RuntimeError("graph_pool_fwd: X and P must share one dtype and have unit-stride rows")
+    dev = P.device
+    work = graph_pool_work(V, B, F, op, dev)
+    args = (off.data_ptr(), B, V, F, op, STORAGE[X.dtype], X.data_ptr(), X.stride(0), P.data_ptr(), P.stride(0),
+            None if arg is None else arg.data_ptr(), None if work is None else work.data_ptr(), _stream_of(dev))
+    if _timing is None:
+        rc = lib.sir_graph_pool_fwd(*args)
+    else:
+        with _Timed("sir_graph_pool_fwd", dev):
+            rc = lib.sir_graph_pool_fwd(*args)
+    if rc != 0:
+        _check(rc, lib)
+
+
+def graph_pool_bwd(off, dP, op, dX, arg=None):
+    """dX [V, F] from dP [B, F] (``sir_graph_pool_bwd``); op sum is ``broadcast_nodes``."""
+    lib = _lib if _lib is not None else load()
+    V = dX.shape[0]
+    B, F = dP.shape
+    if dP.dtype is not dX.dtype or dP.stride(1) != 1 or dX.stride(1) != 1:
+        raise RuntimeError("graph_pool_bwd: dP and dX must share one dtype and have unit-stride rows")
+    dev = dX.device
+    args = (off.data_ptr(), B, V, F, op, STORAGE[dP.dtype], dP.data_ptr(), dP.stride(0),
+            None if arg is None else arg.data_ptr(), dX.data_ptr(), dX.stride(0), _stream_of(dev))
+    if _timing is None:
+        rc = lib.sir_graph_pool_bwd(*args)
+    else:
+        with _Timed("sir_graph_pool_bwd", dev):
+            rc = lib.sir_graph_pool_bwd(*args)
+    if rc != 0:
+        _check(rc, lib)
 
 
 def layer_norm_act_fwd(X, weight, bias, eps, act, slope, R, Y, mean, rstd):

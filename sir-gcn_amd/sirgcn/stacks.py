@@ -1,7 +1,8 @@
 """Multi-layer SIRConv stacks: the layer loops of the reference's models, i.e. the callers of the
 hot path for BASELINE configs 1, 2, 3 and 5.
 
-The reference models wrap SIRConv in embeddings, readouts and pooling (out of scope);
+The reference models wrap SIRConv in embeddings and prediction heads (out of scope) and end
+with a graph readout (``sirgcn.readout``: SumPooling / AvgPooling / MaxPooling);
 what reaches the hot path is their per-layer loop, restated here with the conv / norm classes as
 parameters so that the SAME loop runs on the reference's own ``models/conv.py`` / ``models/norm.py``
 (``tests/golden/make_golden.py`` builds the stack fixtures that way) and on this package's

@@ -135,6 +135,37 @@ int main() {
                                                         0.f, f, f, 300, nullptr, f, nullptr), SIR_EUNSUPPORTED, "H");
     expect("max_bwd_src: NULL perm", sir_edge_max_bwd_src(p, p, nullptr, p, 1, nullptr, 0, 64, 64, f, 64, f, 64, f, 64,
                                                           p, 64, 1, 0.f, f, f, 64, nullptr, nullptr), SIR_EINVAL, "perm");
+    // graph readout
+    const int64_t* off = reinterpret_cast<const int64_t*>(buf.data());
+    expect("pool_fwd: F out of range", sir_graph_pool_fwd(off, 2, 8, 65537, SIR_POOL_SUM, 0, v, 1 << 17, v, 1 << 17, nullptr,
+                                                          nullptr, nullptr), SIR_EINVAL, "sir_graph_pool_fwd: F must be");
+    expect("pool_fwd: negative B", sir_graph_pool_fwd(off, -1, 8, 8, SIR_POOL_SUM, 0, v, 8, v, 8, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "B and V");
+    expect("pool_fwd: ld < F", sir_graph_pool_fwd(off, 2, 8, 8, SIR_POOL_SUM, 0, v, 7, v, 8, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "leading");
+    expect("pool_fwd: bad op", sir_graph_pool_fwd(off, 2, 8, 8, 3, 0, v, 8, v, 8, p, nullptr, nullptr), SIR_EINVAL, "op must be");
+    expect("pool_fwd: bad dtype", sir_graph_pool_fwd(off, 2, 8, 8, SIR_POOL_MEAN, 3, v, 8, v, 8, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "dtype must be");
+    expect("pool_fwd: NULL P", sir_graph_pool_fwd(off, 2, 8, 8, SIR_POOL_MEAN, 0, v, 8, nullptr, 8, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "NULL");
+    expect("pool_fwd: MAX needs arg", sir_graph_pool_fwd(off, 2, 8, 8, SIR_POOL_MAX, 1, v, 8, v, 8, nullptr, nullptr, nullptr),
+           SIR_EINVAL, "MAX needs arg");
+    expect("pool_fwd: work needed", sir_graph_pool_fwd(off, 2, SIR_POOL_SLAB_ROWS + 1, 8, SIR_POOL_MAX, 2, v, 8, v, 8, p, nullptr,
+                                                       nullptr), SIR_EINVAL, "work needed");
+    expect("pool_bwd: ld < F", sir_graph_pool_bwd(off, 2, 8, 8, SIR_POOL_SUM, 0, v, 8, nullptr, v, 7, nullptr), SIR_EINVAL,
+           "sir_graph_pool_bwd: leading");
+    expect("pool_bwd: NULL dP", sir_graph_pool_bwd(off, 2, 8, 8, SIR_POOL_SUM, 0, nullptr, 8, nullptr, v, 8, nullptr), SIR_EINVAL,
+           "NULL");
+    expect("pool_bwd: MAX needs arg", sir_graph_pool_bwd(off, 2, 8, 8, SIR_POOL_MAX, 0, v, 8, nullptr, v, 8, nullptr), SIR_EINVAL,
+           "MAX needs arg");
+    for (int op = 0; op < 3; ++op) {
+        expect("pool_fwd: no graphs is a no-op", sir_graph_pool_fwd(nullptr, 0, 0, 75, op, 0, nullptr, 75, nullptr, 75, nullptr,
+                                                                   nullptr, nullptr), SIR_OK);
+        expect("pool_bwd: no graphs is a no-op", sir_graph_pool_bwd(nullptr, 0, 0, 75, op, 0, nullptr, 75, nullptr, nullptr, 75,
+                                                                   nullptr), SIR_OK);
+    }
+    expect("pool_work_floats: range", (int)sir_graph_pool_work_floats(8, 2, 65537, SIR_POOL_SUM), -1);
+    expect("pool_work_floats: one slab", (int)sir_graph_pool_work_floats(SIR_POOL_SLAB_ROWS, 2, 8, SIR_POOL_MAX), 0);
     std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "ok", failures);
     return failures ? 1 : 0;
 }

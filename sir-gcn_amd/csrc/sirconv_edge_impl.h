@@ -119,102 +119,6 @@ __device__ __forceinline__ void drop_vec(const Drop& d, int64_t row, int c0, flo
 }
 
 // ------------------------------------------------------------------------------ vectors
-// Cache-policy experiment knobs (tools/edge_ab.py builds them as separate libraries):
-//   SIR_NT_STREAM = 1: non-temporal loads/stores for the once-touched row-side streams
-//                      (Q/G rows read, S/dQ/dK/partial rows and the sign mask written);
-//   SIR_NT_GATHER = 1: non-temporal loads for the gathered rows too.
-#ifndef SIR_NT_STREAM
-#define SIR_NT_STREAM 0
-#endif
-#ifndef SIR_NT_GATHER
-#define SIR_NT_GATHER 0
-#endif
-#ifndef SIR_FWD_PF
-#define SIR_FWD_PF 1            // row-CSR edge loop (full-wave rows, fp32): next batch's col[] prefetched per lane
-#endif
-#ifndef SIR_FWD_BUFGATHER
-#define SIR_FWD_BUFGATHER 1     // fp32 forward (mask mode): K rows gathered by 16-B buffer loads (not narrowed)
-#endif
-#ifndef SIR_MASK_WRITELANE
-#define SIR_MASK_WRITELANE 1    // forward sign-mask words built by v_writelane (1) or per-lane selects (0)
-#endif
-typedef float sir_f4 __attribute__((ext_vector_type(4)));
-
-template <int VW, bool NT>
-__device__ __forceinline__ void vload_p(float (&d)[VW], const float* __restrict__ p) {
-    if constexpr (VW == 4 && NT) {
-        const sir_f4 t = __builtin_nontemporal_load(reinterpret_cast<const sir_f4*>(p));
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else if constexpr (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-#pragma unroll
-        for (int w = 0; w < VW; ++w) d[w] = NT ? __builtin_nontemporal_load(p + w) : p[w];
-    }
-}
-
-template <int VW, bool NT>
-__device__ __forceinline__ void vstore_p(float* __restrict__ p, const float (&s)[VW]) {
-    if constexpr (VW == 4 && NT) {
-        sir_f4 t;
-        t.x = s[0]; t.y = s[1]; t.z = s[2]; t.w = s[3];
-        __builtin_nontemporal_store(t, reinterpret_cast<sir_f4*>(p));
-    } else if constexpr (VW == 4) {
-        *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]);
-    } else {
-#pragma unroll
-        for (int w = 0; w < VW; ++w) {
-            if constexpr (NT) __builtin_nontemporal_store(s[w], p + w);
-            else p[w] = s[w];
-        }
-    }
-}
-
-// typed loads / stores: fp32 as above; 16-bit storage as one 8-B access per 4 values
-template <int ST, int VW, bool NT>
-__device__ __forceinline__ void tload_p(float (&d)[VW], const typename Stor<ST>::T* __restrict__ p) {
-    if constexpr (ST == ST_F32) {
-        vload_p<VW, NT>(d, p);
-    } else if constexpr (VW == 4) {
-        const sir_u2* q = reinterpret_cast<const sir_u2*>(p);
-        const sir_u2 t = NT ? __builtin_nontemporal_load(q) : *q;
-        d[0] = h2f<ST>(t.x & 0xffffu); d[1] = h2f<ST>(t.x >> 16);
-        d[2] = h2f<ST>(t.y & 0xffffu); d[3] = h2f<ST>(t.y >> 16);
-    } else {
-        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
-#pragma unroll
-        for (int w = 0; w < VW; ++w) d[w] = h2f<ST>(q[w]);
-    }
-}
-
-template <int ST, int VW, bool NT>
-__device__ __forceinline__ void tstore_p(typename Stor<ST>::T* __restrict__ p, const float (&s)[VW]) {
-    if constexpr (ST == ST_F32) {
-        vstore_p<VW, NT>(p, s);
-    } else if constexpr (VW == 4) {
-        sir_u2 t;
-        t.x = f2h<ST>(s[0]) | (f2h<ST>(s[1]) << 16);
-        t.y = f2h<ST>(s[2]) | (f2h<ST>(s[3]) << 16);
-        if constexpr (NT) __builtin_nontemporal_store(t, reinterpret_cast<sir_u2*>(p));
-        else *reinterpret_cast<sir_u2*>(p) = t;
-    } else {
-        uint16_t* q = reinterpret_cast<uint16_t*>(p);
-#pragma unroll
-        for (int w = 0; w < VW; ++w) q[w] = (uint16_t)f2h<ST>(s[w]);
-    }
-}
-
-// row-side streams (read or written once) and gathered rows
-template <int ST, int VW>
-__device__ __forceinline__ void vload_row(float (&d)[VW], const typename Stor<ST>::T* __restrict__ p) { tload_p<ST, VW, SIR_NT_STREAM>(d, p); }
-template <int ST, int VW>
-__device__ __forceinline__ void vstore_row(typename Stor<ST>::T* __restrict__ p, const float (&s)[VW]) { tstore_p<ST, VW, SIR_NT_STREAM>(p, s); }
-template <int VW>
-__device__ __forceinline__ void vstore_part(float* __restrict__ p, const float (&s)[VW]) { vstore_p<VW, SIR_NT_STREAM>(p, s); }
-template <int ST, int VW>
-__device__ __forceinline__ void vload_gather(float (&d)[VW], const typename Stor<ST>::T* __restrict__ p) { tload_p<ST, VW, SIR_NT_GATHER>(d, p); }
-
 template <int VW>
 __device__ __forceinline__ void vload(float (&d)[VW], const float* __restrict__ p) {
     if constexpr (VW == 4) {
@@ -235,6 +139,47 @@ __device__ __forceinline__ void vstore(float* __restrict__ p, const float (&s)[V
         for (int w = 0; w < VW; ++w) p[w] = s[w];
     }
 }
+
+// typed loads / stores: fp32 as above; 16-bit storage as one 8-B access per 4 values
+template <int ST, int VW>
+__device__ __forceinline__ void tload_p(float (&d)[VW], const typename Stor<ST>::T* __restrict__ p) {
+    if constexpr (ST == ST_F32) {
+        vload<VW>(d, p);
+    } else if constexpr (VW == 4) {
+        const sir_u2* q = reinterpret_cast<const sir_u2*>(p);
+        const sir_u2 t = *q;
+        d[0] = h2f<ST>(t.x & 0xffffu); d[1] = h2f<ST>(t.x >> 16);
+        d[2] = h2f<ST>(t.y & 0xffffu); d[3] = h2f<ST>(t.y >> 16);
+    } else {
+        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
+#pragma unroll
+        for (int w = 0; w < VW; ++w) d[w] = h2f<ST>(q[w]);
+    }
+}
+
+template <int ST, int VW>
+__device__ __forceinline__ void tstore_p(typename Stor<ST>::T* __restrict__ p, const float (&s)[VW]) {
+    if constexpr (ST == ST_F32) {
+        vstore<VW>(p, s);
+    } else if constexpr (VW == 4) {
+        sir_u2 t;
+        t.x = f2h<ST>(s[0]) | (f2h<ST>(s[1]) << 16);
+        t.y = f2h<ST>(s[2]) | (f2h<ST>(s[3]) << 16);
+        *reinterpret_cast<sir_u2*>(p) = t;
+    } else {
+        uint16_t* q = reinterpret_cast<uint16_t*>(p);
+#pragma unroll
+        for (int w = 0; w < VW; ++w) q[w] = (uint16_t)f2h<ST>(s[w]);
+    }
+}
+
+// row-side streams (read or written once) and gathered rows
+template <int ST, int VW>
+__device__ __forceinline__ void vload_row(float (&d)[VW], const typename Stor<ST>::T* __restrict__ p) { tload_p<ST, VW>(d, p); }
+template <int ST, int VW>
+__device__ __forceinline__ void vstore_row(typename Stor<ST>::T* __restrict__ p, const float (&s)[VW]) { tstore_p<ST, VW>(p, s); }
+template <int ST, int VW>
+__device__ __forceinline__ void vload_gather(float (&d)[VW], const typename Stor<ST>::T* __restrict__ p) { tload_p<ST, VW>(d, p); }
 
 // lane K of v takes the wave-uniform x (v_writelane_b32; this clang has no builtin for it)
 // (k must fold to a constant after unrolling: an inline-constant lane select, no hazard)
@@ -267,7 +212,7 @@ __device__ __forceinline__ void edge_batch(int e, const int* __restrict__ col,
     int u[UU];
 #pragma unroll
     for (int i = 0; i < UU; ++i) u[i] = (upre != nullptr) ? upre[i] : col[e + i];
-    constexpr bool kBufGather = SIR_FWD_BUFGATHER && MODE == MODE_FWD && ST == ST_F32 && VW == 4 && LPR == 64 && MASKW;
+    constexpr bool kBufGather = MODE == MODE_FWD && ST == ST_F32 && VW == 4 && LPR == 64 && MASKW;
     constexpr int MWS = sub_mask_words<LPR, VW>();
     uint32_t mr[MASKR ? UU : 1][MWS];
     if constexpr (MASKR) {
@@ -374,7 +319,6 @@ __device__ __forceinline__ void edge_batch(int e, const int* __restrict__ col,
         static_assert(LPR == 64 && VW == 4, "mask layout needs full-wave rows of float4");
         constexpr int NW = NV * VW;
         static_assert(UU * NW <= 64, "one mask store per batch");
-#if SIR_MASK_WRITELANE
         // The compare IS the ballot (v_cmp writes the 64-lane mask to SGPRs; the row's column-range
         // mask is ANDed on the scalar unit) and v_writelane drops each word into its lane: 3 VALU
         // per word.  The select form (lane == k ? b : mine) compiled to ~8 VALU per word (the compare
@@ -395,24 +339,8 @@ __device__ __forceinline__ void edge_batch(int e, const int* __restrict__ col,
             }
         }
         const uint64_t mine = ((uint64_t)mhi << 32) | mlo;
-#else
-        uint64_t mine = 0;
-#pragma unroll
-        for (int i = 0; i < UU; ++i) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const bool ok = (li + LPR * j) < HC;
-#pragma unroll
-                for (int w = 0; w < VW; ++w) {
-                    const uint64_t b = __ballot(ok && (rv[j][w] + cv[i][j][w]) > 0.f);
-                    mine = (lane == i * NW + j * VW + w) ? b : mine;
-                }
-            }
-        }
-#endif
         if (lane < UU * NW) {
-            if constexpr (SIR_NT_STREAM) __builtin_nontemporal_store(mine, mask + (int64_t)e * NW + lane);
-            else mask[(int64_t)e * NW + lane] = mine;
+            mask[(int64_t)e * NW + lane] = mine;
         }
     }
 #pragma unroll
@@ -529,7 +457,7 @@ edge_wave(int64_t wave, const int* __restrict__ rowptr, const int* __restrict__ 
     if constexpr (AGG == AGG_SYM) nr = norm_row[row];
 
     int e = e0;
-    if constexpr (SIR_FWD_PF && LPR == 64 && ST == ST_F32) {
+    if constexpr (LPR == 64 && ST == ST_F32) {
         // software-pipelined column indices (as in the dK pass): the next batch's col[] by one
         // per-lane load issued with the current batch's gathers, moved to SGPRs by v_readlane
         // (S2 forward f32 sum -2 %, mean -2 %, sym -1 %; 16-bit storage +10 %: fp32 only,
@@ -614,7 +542,7 @@ edge_wave(int64_t wave, const int* __restrict__ rowptr, const int* __restrict__ 
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int c = li + LPR * j;
-            if (c < HC) vstore_part<VW>(pp + c * VW, acc[j]);
+            if (c < HC) vstore<VW>(pp + c * VW, acc[j]);
         }
     }
 }
@@ -667,15 +595,9 @@ __device__ __forceinline__ float sel_mask(uint64_t m, float t, float slope) {
     else return lane_select(m, t * slope, t);
 }
 
-#ifndef SIR_DK_PF
-#define SIR_DK_PF 1             // dK pass: the next batch's col / perm indices loaded with the current batch's rows
-#endif
 
 // wave-uniform (scalar) edge indices of one batch: source / destination id and dst-CSR position
 template <int UU> struct EdgeIdx { int v[UU]; int p[UU]; };
-#ifndef SIR_DQ_VMASK
-#define SIR_DQ_VMASK 1          // dQ pass: mask words by one vector load + v_readlane (1; -9% sum, -19% sym) or scalar loads (0)
-#endif
 
 template <int ST, int MODE, int ACT, int AGG, int NV, int UU, bool PRE = false, bool PIDX = false>
 __device__ __forceinline__ void mask_batch(int e, const int* __restrict__ col, const int* __restrict__ perm,
@@ -703,7 +625,7 @@ __device__ __forceinline__ void mask_batch(int e, const int* __restrict__ col, c
     }
     uint64_t wd[UU][NW];
     if constexpr (PRE) {
-        // words already in registers (one per lane, prefetched by mask_item_dst): edge e's word
+        // words already in registers (one per lane, prefetched by mask_item_dst_wide): edge e's word
         // k is in lane pre_lane + i*NW + k
         const int mlo = (int)(uint32_t)pre, mhi = (int)(uint32_t)(pre >> 32);
 #pragma unroll
@@ -714,7 +636,7 @@ __device__ __forceinline__ void mask_batch(int e, const int* __restrict__ col, c
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane(mhi, pre_lane + i * NW + k);
                 wd[i][k] = ((uint64_t)hi << 32) | lo;
             }
-    } else if constexpr (SIR_DQ_VMASK && MODE == MODE_BWD_DST && UU * NW <= 64) {
+    } else if constexpr (MODE == MODE_BWD_DST && UU * NW <= 64) {
         // the batch's UU*NW words are contiguous: one 8-B vector load per lane, then broadcast
         // each word to SGPRs (v_readlane) for the lane-mask selects
         const uint64_t mv = (lane < UU * NW) ? mask[(int64_t)e * NW + lane] : 0ull;
@@ -782,7 +704,7 @@ __device__ __forceinline__ void mask_item(int e0, int e1, const int* __restrict_
                                           const float* __restrict__ norm_col, float nr, float slope,
                                           int lane, int HC, const float (&gv)[NV][4], float (&acc)[NV][4]) {
     int e = e0;
-    if constexpr (SIR_DK_PF && MODE == MODE_BWD_SRC) {
+    if constexpr (MODE == MODE_BWD_SRC) {
         // software-pipelined indices: the next batch's col / perm are fetched by one per-lane
         // vector load (lane i < U: edge eb + i, clamped to the item) issued with the current
         // batch's mask words and rows, and moved to SGPRs by v_readlane when the batch starts; a
@@ -835,55 +757,12 @@ __device__ __forceinline__ void mask_item(int e0, int e1, const int* __restrict_
         mask_batch<ST, MODE, ACT, AGG, NV, 1>(e, col, perm, G, ldg, mask, norm_col, nr, slope, lane, HC, gv, acc);
 }
 
-#ifndef SIR_DQ_PF
-#define SIR_DQ_PF 1             // dQ pass: next batch's mask words loaded before the current batch is summed
-#endif
 
-// dQ pass (no col/perm reads for sum/mean): the mask words of the NEXT U-edge batch are loaded
-// while the current batch is summed, so a wave no longer waits one memory latency per batch.
-// A full batch is loaded whole; the row's final partial batch (and a row shorter than U) is
-// loaded lane-guarded, so no load leaves the row.  Every batch's words start at lane 0, so the
-// readlane lane indices are compile-time constants (a runtime lane index costs ~20%); the final
-// partial batch is summed edge by edge under uniform guards.
-template <int ST, int ACT, int AGG, int NV, int U>
-__device__ __forceinline__ void mask_item_dst(int e0, int e1, const int* __restrict__ col,
-                                              const uint64_t* __restrict__ mask,
-                                              const float* __restrict__ norm_col, float nr, float slope,
-                                              int lane, int HC, const float (&gv)[NV][4], float (&acc)[NV][4]) {
-    constexpr int NW = NV * 4, BW = U * NW;       // words per edge, per batch (BW <= 64)
-    const int wl = lane % BW;
-    auto load_batch = [&](int eb) -> uint64_t {
-        const int n = e1 - eb;
-        if (n >= U) return mask[(int64_t)eb * NW + wl];
-        return (lane < n * NW) ? mask[(int64_t)eb * NW + lane] : 0ull;
-    };
-    uint64_t cur = load_batch(e0);
-    int e = e0;
-    for (; e + U <= e1; e += U) {
-        const uint64_t nxt = load_batch(e + U);
-        mask_batch<ST, MODE_BWD_DST, ACT, AGG, NV, U, true>(e, col, nullptr, nullptr, 0, mask, norm_col, nr, slope,
-                                                        lane, HC, gv, acc, cur, 0);
-        cur = nxt;
-    }
-    const int r = e1 - e;                         // 0 .. U-1 edges left, their words in cur
-#pragma unroll
-    for (int i = 0; i < U - 1; ++i)
-        if (i < r)
-            mask_batch<ST, MODE_BWD_DST, ACT, AGG, NV, 1, true>(e + i, col, nullptr, nullptr, 0, mask, norm_col, nr,
-                                                            slope, lane, HC, gv, acc, cur, i * NW);
-}
-
-#ifndef SIR_DQ_WIDE
-#define SIR_DQ_WIDE 1           // dQ pass: a whole wave of mask words per load (mask_item_dst_wide)
-#endif
-
-// dQ pass, wide form: the per-batch loads of mask_item_dst leave a wave one U-edge batch (U*NW*8 B)
-// in flight, so a row of ~20 edges costs ~4 serial memory latencies and the pass is latency-bound.
-// Here every load fetches a full chunk of CH = 64/NW edges (all 64 lanes: 512 B for H = 256), the
+// dQ pass: loads of one U-edge batch (U*NW*8 B) at a time leave a row of ~20 edges ~4 serial memory
+// latencies, and the pass latency-bound.  Here every load fetches a full chunk of CH = 64/NW edges (all 64 lanes: 512 B for H = 256), the
 // row's first two chunks are loaded together and the next chunk is in flight while one is summed (a
 // row of <= 2*CH edges costs one latency); a chunk is summed in SB-edge sub-batches
-// (compile-time readlane lanes, SB*NW word pairs of SGPRs).  Same per-column edge order as
-// mask_item_dst, so the sums are bit-identical.
+// (compile-time readlane lanes, SB*NW word pairs of SGPRs), in the edge order of mask_item.
 template <int ST, int ACT, int AGG, int NV>
 __device__ __forceinline__ void mask_item_dst_wide(int e0, int e1, const int* __restrict__ col,
                                                    const uint64_t* __restrict__ mask,
@@ -955,68 +834,6 @@ __device__ __forceinline__ void mask_item_dst_wide(int e0, int e1, const int* __
     }
 }
 
-#ifndef SIR_DQ_SMEM
-#define SIR_DQ_SMEM 0           // 1: dQ pass (sum / mean, H <= 256) mask words by prefetched scalar loads (+13 %: rejected, profiles/r02_ab_dq_smem2.txt)
-#endif
-
-// dQ pass, scalar form (sum / mean, NV = 1: 4 words per edge): the mask words of a 4-edge
-// sub-batch (128 B, contiguous) come by two s_load_dwordx16 straight into SGPRs — the selects'
-// lane-mask operands — so no v_readlane is needed (8 per edge in the vector forms: the pass was
-// VALU-bound on them).  Scalar loads may return out of order (one lgkmcnt for all), so the next
-// sub-batch's loads are issued only after the current one's words have arrived, then overlap
-// its selects and adds.  Same per-column edge order as the other forms: bit-identical.
-template <int ST, int ACT, int AGG>
-__device__ __forceinline__ void mask_item_dst_smem(int e0, int e1, const uint64_t* __restrict__ mask, float slope,
-                                                   int HC, int lane, const float (&gv)[1][4], float (&acc)[1][4]) {
-    struct W16 { uint64_t w[16]; };
-    auto load = [&](int eb) {
-        W16 x;
-        const uint64_t* p = mask + (int64_t)__builtin_amdgcn_readfirstlane(eb) * 4;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) x.w[k] = p[k];
-        return x;
-    };
-    auto arrived = [&](const W16& x) {       // wait for x (and nothing else is in flight)
-#pragma unroll
-        for (int k = 0; k < 16; ++k) asm volatile("" :: "s"(x.w[k]) : "memory");
-    };
-    const bool ok = lane < HC;
-    auto compute = [&](const W16& x, int n) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < n && ok) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) acc[0][w] += sel_mask<ACT>(x.w[4 * i + w], gv[0][w], slope);
-            }
-        }
-    };
-    int e = e0;
-    if (e + 4 <= e1) {
-        W16 a = load(e);
-        for (; e + 8 <= e1; e += 8) {
-            arrived(a);
-            const W16 b = load(e + 4);
-            compute(a, 4);
-            arrived(b);
-            if (e + 12 <= e1) a = load(e + 8);
-            compute(b, 4);
-        }
-        if (e + 4 <= e1) {
-            arrived(a);
-            compute(a, 4);
-            e += 4;
-        }
-    }
-    for (; e < e1; ++e) {                    // 0 .. 3 edges
-        uint64_t wd[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) wd[k] = uniform64(mask[(int64_t)e * 4 + k]);
-        if (ok) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) acc[0][w] += sel_mask<ACT>(wd[w], gv[0][w], slope);
-        }
-    }
-}
 
 __device__ __forceinline__ int4 uniform_item(const int4* __restrict__ items, int64_t i) {
     int4 it = items[i];
@@ -1071,12 +888,8 @@ mask_pass_item(int64_t wave, const int* __restrict__ rowptr, const int* __restri
     }
     float nr = 1.f;
     if constexpr (AGG == AGG_SYM) nr = norm_row[row];
-    if constexpr (SIR_DQ_SMEM && MODE == MODE_BWD_DST && AGG != AGG_SYM && NV == 1)
-        mask_item_dst_smem<ST, ACT, AGG>(e0, e1, mask, slope, HC, lane, gv, acc);
-    else if constexpr (SIR_DQ_WIDE && MODE == MODE_BWD_DST)
+    if constexpr (MODE == MODE_BWD_DST)
         mask_item_dst_wide<ST, ACT, AGG, NV>(e0, e1, col, mask, norm_col, nr, slope, lane, HC, gv, acc);
-    else if constexpr (SIR_DQ_PF && MODE == MODE_BWD_DST && AGG != AGG_SYM && U * NV * 4 <= 64)
-        mask_item_dst<ST, ACT, AGG, NV, U>(e0, e1, col, mask, norm_col, nr, slope, lane, HC, gv, acc);
     else
         mask_item<ST, MODE, ACT, AGG, NV, U>(e0, e1, col, perm, G, ldg, mask, norm_col, nr, slope, lane, HC, gv, acc);
     if (slot < 0) {
@@ -1095,7 +908,7 @@ mask_pass_item(int64_t wave, const int* __restrict__ rowptr, const int* __restri
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int c = lane + 64 * j;
-            if (c < HC) vstore_part<4>(op + c * 4, acc[j]);
+            if (c < HC) vstore<4>(op + c * 4, acc[j]);
         }
     }
 }
@@ -1115,9 +928,6 @@ k_edge_mask(const int* __restrict__ rowptr, const int* __restrict__ col, const i
                                               out, ldo, partial, Gm, ldgm, drop);
 }
 
-#ifndef SIR_DUAL_PRIO
-#define SIR_DUAL_PRIO 0         // one-launch backward wave priority: 1 = dK waves first, 2 = dQ waves first
-#endif
 // Both sign-mask backward passes in ONE launch (SUM / SYM: the dK pass does not need the dQ pass's
 // Gm).  The dQ pass is VALU-bound (v_readlane + select + add per element and edge) and reads 32 B
 // per edge; the dK pass is HBM-bound (one gathered G row per edge).  Interleaving their waves
@@ -1153,11 +963,6 @@ k_edge_mask_dual(const int* __restrict__ rowptr, const int* __restrict__ col, co
         idx = nmin + (w - 2 * nmin);
         if (idx >= (dst ? n_items : n_items_s)) return;
     }
-#if SIR_DUAL_PRIO == 1
-    if (!dst) __builtin_amdgcn_s_setprio(1);       // dK waves (memory-bound) issue first
-#elif SIR_DUAL_PRIO == 2
-    if (dst) __builtin_amdgcn_s_setprio(1);        // dQ waves (VALU-bound) issue first
-#endif
     if (dst)
         mask_pass_item<ST, MODE_BWD_DST, ACT, AGG, NV, UD>(idx, rowptr, col, nullptr, items, G, ldg, mask, in_norm,
                                                            out_norm, slope, H, dQ, lddq, partial, nullptr, H, drop_q);
@@ -1228,11 +1033,11 @@ k_combine(const int4* __restrict__ splits, const float* __restrict__ partial,
             if (drop.on()) drop_vec<ST, VW>(drop, sp.x, c * VW, r);      // backward passes only (host)
             if (accumulate) {           // segmented forward: prior S row + this segment's sum
                 float prev[VW];
-                tload_p<ST, VW, false>(prev, out + (int64_t)sp.x * ldo + c * VW);
+                tload_p<ST, VW>(prev, out + (int64_t)sp.x * ldo + c * VW);
 #pragma unroll
                 for (int w = 0; w < VW; ++w) r[w] = prev[w] + r[w];
             }
-            tstore_p<ST, VW, false>(out + (int64_t)sp.x * ldo + c * VW, r);
+            tstore_p<ST, VW>(out + (int64_t)sp.x * ldo + c * VW, r);
         }
         __syncthreads();
     }

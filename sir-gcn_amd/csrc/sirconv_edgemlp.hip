@@ -82,20 +82,6 @@ __device__ __forceinline__ float mlp_pow2(int e) {
 __device__ __forceinline__ int mlp_scale_exp(float m) { const int s = 15 - mlp_bexp(m); return s > 126 ? 126 : s; }
 // fragment image of one 16-k step plane: piece (row, h) of 16 B at (row / 32) * 1024 + h * 512 + (row % 32) * 16
 __device__ __forceinline__ int mlp_fimg(int row, int h) { return ((row >> 5) << 10) + (h << 9) + ((row & 31) << 4); }
-// The stream forward's image (32 rows): mlp_fimg with the row's 16-B slot XORed by f = 2 (g & 3) + h.  A
-// staging store (ds_write_b64, one edge row a wave, lane l: k-group g = l / 4, half h = (l / 2) & 1) then
-// puts the 16 lanes of each store group on 16 distinct 8-B positions of the 128-B bank period (unswizzled:
-// all on the row's one slot, 8-way), and the MFMA fragment read (lane l: row l & 31, half l / 32, one g a
-// read) still takes 32 distinct slots of its 512-B half (the XOR is a bijection on the slot).
-#ifndef SIR_MLP_SWZ
-#define SIR_MLP_SWZ 1
-#endif
-#ifndef SIR_MLP_SPLIT_WALK
-#define SIR_MLP_SPLIT_WALK 1    // stream max forward: interior tiles walked by both half-waves (16 edges each)
-#endif
-#ifndef SIR_MLP_SPLIT_MIX
-#define SIR_MLP_SPLIT_MIX 1     // stream forward staging: hi / lo split by v_fma_mix (2 VALU per element)
-#endif
 // hi = fp16(x s), lo = fp16(x s - hi) of 4 floats (s an exact power of two), one v_fma_mix each into the
 // halves of the packed registers: x s is exact and x s - hi exact inside the fused op, so the bits are
 // those of rounding y = x s and y - hi separately.  s_nop 1: VALU-write wait states the hazard recognizer
@@ -113,8 +99,13 @@ __device__ inline void split4_mix(float4 a, float s, uint2& hi, uint2& lo) {
     hi = make_uint2(h0, h1);
     lo = make_uint2(l0, l1);
 }
+// The stream forward's image (32 rows): mlp_fimg with the row's 16-B slot XORed by f = 2 (g & 3) + h.  A
+// staging store (ds_write_b64, one edge row a wave, lane l: k-group g = l / 4, half h = (l / 2) & 1) then
+// puts the 16 lanes of each store group on 16 distinct 8-B positions of the 128-B bank period (unswizzled:
+// all on the row's one slot, 8-way), and the MFMA fragment read (lane l: row l & 31, half l / 32, one g a
+// read) still takes 32 distinct slots of its 512-B half (the XOR is a bijection on the slot).
 __device__ __forceinline__ int mlp_fimg_sw(int row, int h, int g) {
-    return (h << 9) + (((row & 31) << 4) ^ (SIR_MLP_SWZ ? ((h << 4) | ((g & 3) << 5)) : 0));
+    return (h << 9) + (((row & 31) << 4) ^ ((h << 4) | ((g & 3) << 5)));
 }
 
 // pack: out16[((t * NG + g) * 2 + p) * 64 + l] = 8 halves of part p (hi / lo) of W[32t + l%32][16g + 8(l/32) + j]
@@ -216,7 +207,7 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
         const int k = 256 * c + 4 * l;
         if constexpr (X16) {
             float t4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (k < H) tload_p<ST, 4, false>(t4, qp + k);
+            if (k < H) tload_p<ST, 4>(t4, qp + k);
             q4[c] = make_float4(t4[0], t4[1], t4[2], t4[3]);
         } else {
             q4[c] = (k < H) ? *reinterpret_cast<const float4*>(qp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -236,7 +227,7 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
                 const int k = 256 * c + 4 * l;
                 if constexpr (X16) {
                     float t4[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (k < H) tload_p<ST, 4, false>(t4, K + (int64_t)u * ldk + k);
+                    if (k < H) tload_p<ST, 4>(t4, K + (int64_t)u * ldk + k);
                     kv[ii][c] = make_float4(t4[0], t4[1], t4[2], t4[3]);
                 } else {
                     kv[ii][c] = (k < H) ? *reinterpret_cast<const float4*>(K + (int64_t)u * ldk + k)
@@ -853,9 +844,9 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
             const int r = __builtin_amdgcn_readlane(rowv, w + NW * ii);
             if constexpr (X16) {
                 float t4[4];
-                tload_p<ST, 4, false>(t4, K + (int64_t)u * ldk + k4);
+                tload_p<ST, 4>(t4, K + (int64_t)u * ldk + k4);
                 kv[ii] = make_float4(t4[0], t4[1], t4[2], t4[3]);
-                tload_p<ST, 4, false>(t4, Q + (int64_t)r * ldq + k4);
+                tload_p<ST, 4>(t4, Q + (int64_t)r * ldq + k4);
                 qv[ii] = make_float4(t4[0], t4[1], t4[2], t4[3]);
             } else {
                 kv[ii] = *reinterpret_cast<const float4*>(K + (int64_t)u * ldk + k4);
@@ -883,19 +874,10 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
             const float m = wave_max64(fmaxf(fmaxf(fabsf(a4.x), fabsf(a4.y)), fmaxf(fabsf(a4.z), fabsf(a4.w))));
             const int se = mlp_scale_exp(m);
             const float sc = mlp_pow2(se);
-            if constexpr (SIR_MLP_SPLIT_MIX) {
-                uint2 hv, lv;
-                split4_mix(a4, sc, hv, lv);
-                *reinterpret_cast<uint2*>(d) = hv;
-                *reinterpret_cast<uint2*>(d + 1024) = lv;
-            } else {
-                const float y[4] = {a4.x * sc, a4.y * sc, a4.z * sc, a4.w * sc};
-                _Float16 hv[4], lv[4];
-#pragma unroll
-                for (int x = 0; x < 4; ++x) { hv[x] = (_Float16)y[x]; lv[x] = (_Float16)(y[x] - (float)hv[x]); }
-                *reinterpret_cast<uint2*>(d) = __builtin_bit_cast(uint2, hv);
-                *reinterpret_cast<uint2*>(d + 1024) = __builtin_bit_cast(uint2, lv);
-            }
+            uint2 hv, lv;
+            split4_mix(a4, sc, hv, lv);
+            *reinterpret_cast<uint2*>(d) = hv;
+            *reinterpret_cast<uint2*>(d + 1024) = lv;
             if (l == 0) sInv[bf][i] = mlp_pow2(-se);
         }
         if (w == 0 && l < 32) sC[bf][l] = (l < nv) ? ((RED == AGG_SYM) ? cn : 1.f) : 0.f;
@@ -961,7 +943,7 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
         const int r_next = __shfl(rowv0, (li + 1) & 31);
         const bool end_l = li < nv && ((li + 1 < nv ? r_next : next_first) != rowv0 || (li + 1 == nv && t0 + nv == ee));
         const uint32_t bnd = (uint32_t)__builtin_amdgcn_ballot_w64(l < 32 && end_l);
-        if constexpr (RED == 3 && SIR_MLP_SPLIT_WALK) {
+        if constexpr (RED == 3) {
             if (!first_run && t0 + 32 < ee) {
                 // max over a full interior tile (no block-boundary slot can end here): the two half-waves
                 // walk edges 0-15 and 16-31 of the same features.  Half 1's first run may have begun in
@@ -1400,16 +1382,6 @@ int64_t mlp_pack16_bytes(int H, int F) {
     return (int64_t)FP * mlp_ng(H) * 16 * 2 * 2 + (int64_t)FP * 4;
 }
 
-#ifndef SIR_MLP_RESIDENT
-// 1: H <= 128, F <= 256 on k_mlp_fwd16p (weights resident in registers, persistent blocks): cfg1 0.302 ->
-// 0.294 ms; at H = 256 it was slower than the per-item kernel (S1 max forward 15.5 vs 14.4 ms,
-// profiles/r03_ab_mlp_resident.txt: the W stream from L2 was not the bound), so NG = 16 stays per-item
-#define SIR_MLP_RESIDENT 1
-#endif
-#ifndef SIR_MLP_PIPE
-#define SIR_MLP_PIPE 1          // 1: 128 < H <= 256, F <= 256 on k_mlp_fwd16q (S1 max forward 13.69 -> 10.02 ms,
-                                // profiles/r04_ab_mlp_fwd.txt; at H <= 128 k_mlp_fwd16p stays faster)
-#endif
 // the 16-bit storage forms (max, act2 = identity) on k_mlp_fwd16
 template <int ACT1, int ST>
 hipError_t mlp_fwd16_st(int nt, dim3 grid, hipStream_t st, const EdgeMlpArgs& a, const void* p16) {
@@ -1435,12 +1407,15 @@ hipError_t mlp_fwd16_st(int nt, dim3 grid, hipStream_t st, const EdgeMlpArgs& a,
     return hipGetLastError();
 }
 
+// Forward routes at F <= 256: H <= 128 on k_mlp_fwd16p (weights resident in registers, persistent
+// blocks), 128 < H <= 256 on k_mlp_fwd16q (at H = 256 the resident form was slower than the per-item
+// kernel: the W stream from L2 was not the bound); everything else on the per-item k_mlp_fwd16.
 template <int ACT1, int ACT2, int RED>
 hipError_t mlp_fwd16_nt(int nt, dim3 grid, hipStream_t st, const EdgeMlpArgs& a, const void* p16) {
     const int NG = mlp_ng(a.H), FP = (a.F + 31) / 32 * 32;
     const h8v* w16 = static_cast<const h8v*>(p16);
     const float* winv = reinterpret_cast<const float*>(static_cast<const char*>(p16) + (int64_t)FP * NG * 64);
-    if (SIR_MLP_PIPE && a.col != nullptr && a.F <= 256 && NG == 16) {
+    if (a.col != nullptr && a.F <= 256 && NG == 16) {
         const int ncu = device_cu_count();
         // resident blocks only (a persistent block never yields its CU): one 512-thread block per CU
         const int64_t cap = (int64_t)ncu;
@@ -1455,7 +1430,7 @@ hipError_t mlp_fwd16_nt(int nt, dim3 grid, hipStream_t st, const EdgeMlpArgs& a,
 #undef SIR_MLP_FWD16Q
         return hipGetLastError();
     }
-    if (SIR_MLP_RESIDENT && a.F <= 256 && (NG == 4 || NG == 8)) {
+    if (a.F <= 256 && (NG == 4 || NG == 8)) {
         const int ncu = device_cu_count();
         // resident blocks only (a persistent block never yields its CU): NG = 16 takes ~208 VGPRs (one
         // 512-thread block per CU), NG <= 8 fits two

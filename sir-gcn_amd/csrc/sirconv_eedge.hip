@@ -226,7 +226,7 @@ k_eedge_fwd(const int* __restrict__ col, const int* __restrict__ eidx, int n_ero
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int c = li + LPR * j;
-            if (c < HC) vstore_part<4>(pp + c * 4, acc[j]);
+            if (c < HC) vstore<4>(pp + c * 4, acc[j]);
         }
     }
 }

@@ -45,27 +45,8 @@ typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 
 constexpr int KC = 32;          // contraction elements per LDS stage (two k16 MFMA steps)
 
-#ifndef SIR_ABL_TN
-#define SIR_ABL_TN 0            // timing-only ablation: TN loads dropped (zero-record descriptors)
-#endif
-#ifndef SIR_ABL_NT
-#define SIR_ABL_NT 0            // timing-only ablations: 1 = NT data loads dropped, 2 = NT C stores dropped,
-                                // persistent NT only: 4 = no split arithmetic, 8 = no MFMAs
-#endif
 #ifndef SIR_HR
 #define SIR_HR 8                // headroom bits of a reset running scale (see next_se)
-#endif
-#ifndef SIR_TN_CFG
-#define SIR_TN_CFG 2            // TN tiling: 1 = 16 waves 64x64 (4 per SIMD), 2 = 8 waves 128x64 (2 per SIMD)
-#endif
-#ifndef SIR_TN_PF
-#define SIR_TN_PF 2             // TN chunks in flight in registers (1 or 2; 2: -3..-5 %, profiles/r02_ab_tn_pf2.txt)
-#endif
-#ifndef SIR_NT_PF
-#define SIR_NT_PF 2             // NT chunks in flight in registers ahead of the LDS stage (1 or 2)
-#endif
-#ifndef SIR_NT_EPI
-#define SIR_NT_EPI 1            // 1: NT epilogue through LDS, full-row stores; 0: fragment stores
 #endif
 
 // Smallest e with |m| < 2^e for normal m (e = -126 for 0 and subnormals, 129 for inf/nan).
@@ -127,9 +108,6 @@ k_gate_dact(float* __restrict__ C, int64_t ldc, const float* __restrict__ gate, 
     C[r * ldc + c] = gate_dact(gate[r * ldc + c], C[r * ldc + c], relu, slope);
 }
 
-#ifndef SIR_SPLIT_MIX
-#define SIR_SPLIT_MIX 1         // TN loaders: 1 = the split by v_fma_mix (2 VALU per element), 0 = plain C (~4.5)
-#endif                          // (the NT kernels keep the C form: the asm one costs them a spill in the loop)
 // hi/lo fp16 split of 8 floats scaled by s (exact power of two)
 // hi = fp16(x s), lo = fp16(x s - hi), one v_fma_mix each, written into the halves of the fragment
 // registers (x s is exact, and x s - hi is exact in the fused op: the same bits as rounding y = x s
@@ -153,14 +131,8 @@ __device__ inline void split8_mix(float4 a, float4 b, float s, h8& hi, h8& lo) {
     hi = __builtin_bit_cast(h8, u4{h0, h1, h2, h3});
     lo = __builtin_bit_cast(h8, u4{l0, l1, l2, l3});
 }
-// the same split written as fused ops for the backend's v_fma_mix patterns (x s exact: fma(x, s, -hi)
-// == x s - hi, one rounding to fp16 either way)
-#define SIR_SPLIT1F(x, i) { const _Float16 h_ = (_Float16)__builtin_fmaf((x), s, 0.f); hi[i] = h_; lo[i] = (_Float16)__builtin_fmaf((x), s, -(float)h_); }
-__device__ inline void split8_fma(float4 a, float4 b, float s, h8& hi, h8& lo) {
-    SIR_SPLIT1F(a.x, 0) SIR_SPLIT1F(a.y, 1) SIR_SPLIT1F(a.z, 2) SIR_SPLIT1F(a.w, 3)
-    SIR_SPLIT1F(b.x, 4) SIR_SPLIT1F(b.y, 5) SIR_SPLIT1F(b.z, 6) SIR_SPLIT1F(b.w, 7)
-}
-#undef SIR_SPLIT1F
+// the same split in plain C (~4.5 VALU per element), for k_gemm_nt (the asm form costs it a spill in
+// the loop) and the small kernels
 #define SIR_SPLIT1(x, i) { const float y_ = (x) * s; const _Float16 h_ = (_Float16)y_; hi[i] = h_; lo[i] = (_Float16)(y_ - (float)h_); }
 __device__ inline void split8(float4 a, float4 b, float s, h8& hi, h8& lo) {
     SIR_SPLIT1(a.x, 0) SIR_SPLIT1(a.y, 1) SIR_SPLIT1(a.z, 2) SIR_SPLIT1(a.w, 3)
@@ -237,7 +209,7 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
     // loader role: buffer loads off wave-uniform bases (rows past M read as 0 by the range check)
     const int rho = t / TPR, kp = t % TPR;
     const int64_t rows_here = (M - d0 < BD) ? M - d0 : BD;
-    const rsrc_t arsrc = mk_rsrc(A + d0 * lda, (SIR_ABL_NT & 1) ? 0u : (uint32_t)(rows_here * lda * 4));
+    const rsrc_t arsrc = mk_rsrc(A + d0 * lda, (uint32_t)(rows_here * lda * 4));
     const int aoff = (rho * (int)lda + kp * FPT) * 4;
     const rsrc_t wrsrc = mk_rsrc(Wp, (uint32_t)((int64_t)nc * Npad * 128));
     int woff[WPT];
@@ -255,7 +227,7 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
     const int w = t >> 6, l = t & 63, r = l & 31, h = l >> 5;
     const int d_w = (w / WF) * TDT * 32, f_w = (w % WF) * TFT * 32;
 
-    // register sets for data chunks in flight: chunk j lands in set j % SIR_NT_PF.  The packed
+    // register sets for data chunks in flight: chunk j lands in set j % 2.  The packed
     // weights come from L2 (one set, loaded one chunk ahead).
     float4 dv[2][FPT / 4];
     u4v wv[WPT];
@@ -366,7 +338,6 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
 
     load(0, 0);
     store(0, 0, true);
-#if SIR_NT_PF == 2
     // two data chunks in flight: at step c the registers hold chunks c+1 (set (c+1)&1) and c+2
     // (set c&1); chunk c+1 is split into the free stage, then W(c+2) and A(c+3) (into the freed
     // set) are issued in that order, so that the wait for A(c+1), W(c+1) leaves A(c+2) in flight.
@@ -408,59 +379,8 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
         step_tail(c, 1);
         if (c + 1 < nc) step_tail(c + 1, 0);
     }
-#elif SIR_NT_PF == 3
-    // two data chunks in flight, and the split of chunk c+1 into the free stage happens BEFORE
-    // the MFMAs of chunk c (the free stage was last read before the previous barrier), in one
-    // basic block with them so the scheduler can interleave its VALU/LDS work with the MFMAs.
-    // Issue order per step: W(c+2) then A(c+3), so the next step's wait for A(c+2), W(c+2)
-    // leaves A(c+3) in flight.
-    if (nc > 1) { load_a(1, 1); load_w(1); }
-    if (nc > 2) load_a(0, 2);
-    __syncthreads();
-    auto step_full = [&](int c, int set) {        // requires c + 3 < nc
-        const int buf = c & 1;
-        rescale(buf);
-        store(set, buf ^ 1);
-        load_w(c + 2);
-        load_a(set, c + 3);
-        mfma(buf);
-        __syncthreads();
-    };
-    auto step_tail = [&](int c, int set) {
-        const int buf = c & 1;
-        rescale(buf);
-        if (c + 1 < nc) store(set, buf ^ 1);
-        if (c + 2 < nc) load_w(c + 2);
-        if (c + 3 < nc) load_a(set, c + 3);
-        mfma(buf);
-        __syncthreads();
-    };
-    int c = 0;
-    for (; c + 4 < nc; c += 2) {
-        step_full(c, 1);
-        step_full(c + 1, 0);
-    }
-    for (; c < nc; c += 2) {
-        step_tail(c, 1);
-        if (c + 1 < nc) step_tail(c + 1, 0);
-    }
-#else
-    __syncthreads();
-    for (int c = 0; c < nc; ++c) {
-        const int buf = c & 1;
-        const bool more = c + 1 < nc;
-        if (more) load(0, c + 1);
-        compute(buf);
-        if (more) store(0, buf ^ 1);
-        __syncthreads();
-    }
-#endif
 
     // epilogue: C[m][n] = acc * 2^-se(m) * inv_t[n] + bias[n]
-#if SIR_NT_EPI != 1
-#error "the fragment-store NT epilogue has no dropout"
-#endif
-#if SIR_NT_EPI == 1
     // Through LDS, one 32-row band of every wave per round: the waves write their scaled float4
     // fragments into a row-major image (row pitch BF*4 + 16 B: conflict-free ds_write_b128), then
     // the block stores whole output rows — every wave-instruction writes BF*4 contiguous bytes
@@ -505,41 +425,11 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
             const int64_t m = d0 + (row >> 5) * (TDT * 32) + 32 * b + (row & 31);
             const int n = f0 + c4 * 4;
             const float4 o = *reinterpret_cast<const float4*>(lds + row * PITCH + c4 * 16);
-            if (!(SIR_ABL_NT & 2) && m < M && n < N) *reinterpret_cast<float4*>(C + m * ldc + n) = o;
+            if (m < M && n < N) *reinterpret_cast<float4*>(C + m * ldc + n) = o;
         }
         __syncthreads();
     }
 }
-#else
-    float* sc = reinterpret_cast<float*>(lds);
-    if (kp == 0) sc[rho] = pow2(-se_run);
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < TDT; ++b) {
-        const int dl = d_w + 32 * b + r;
-        const int64_t m = d0 + dl;
-        const float is = sc[dl];
-#pragma unroll
-        for (int a = 0; a < TFT; ++a) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = f0 + f_w + 32 * a + 8 * g + 4 * h;
-                const float4 it = *reinterpret_cast<const float4*>(inv_t + n);
-                float4 o;
-                o.x = acc[a][b][4 * g + 0] * is * it.x;
-                o.y = acc[a][b][4 * g + 1] * is * it.y;
-                o.z = acc[a][b][4 * g + 2] * is * it.z;
-                o.w = acc[a][b][4 * g + 3] * is * it.w;
-                if (bias != nullptr && n < N) {
-                    const float4 bb = *reinterpret_cast<const float4*>(bias + n);
-                    o.x += bb.x; o.y += bb.y; o.z += bb.z; o.w += bb.w;
-                }
-                if (m < M && n < N) *reinterpret_cast<float4*>(C + m * ldc + n) = o;
-            }
-        }
-    }
-}
-#endif
 
 // ------------------------------------------------------------------------------------------
 // Persistent NT GEMM (N <= NT_P_NMAX, K = 32 * NCT).  k_gemm_nt's tiles are short at the layer's
@@ -553,34 +443,8 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
 // past M and columns past N fall outside the store's range and are dropped, so no store is
 // guarded by a branch and the compiler's wait counts stay exact.  Per-tile data and arithmetic
 // are those of k_gemm_nt<2, 4, 4, 2, true>: results are bit-identical.
-#ifndef SIR_NT_PERSIST
-#define SIR_NT_PERSIST 1
-#endif
-#ifndef SIR_NT_PRIO
-#define SIR_NT_PRIO 0           // 1: s_setprio 1 around each step's MFMA cluster; 2: waves 4-7 at priority 1
-#endif
-#ifndef SIR_NT_P_UNROLL
-#define SIR_NT_P_UNROLL 1       // the steps between the first and the last three fully unrolled
-#endif
-#ifndef SIR_NT_STAGGER
-#define SIR_NT_STAGGER 0        // 1: waves 4-7 split / load before their MFMAs (see step)
-#endif
-#ifndef SIR_NT_P_KSB
-#define SIR_NT_P_KSB 1
-#endif
-#ifndef SIR_NT_MAX3
-#define SIR_NT_MAX3 1           // 1: the row maximum of a chunk by v_max3 with |.| modifiers (fmax4_mix)
-#endif
-// hi / lo split of the persistent NT kernel: 1 = v_fma_mix in asm (split8_mix), 2 = the same as fused C ops
-// (split8_fma), 0 = plain C; all bit-identical.  Round-6 A/B over QK / Y / G / dX at S2: 5.71 ms (0) ->
-// 5.57 ms (1 with SIR_NT_MAX3; 2 VGPRs spilled outside the chunk loop), fused C 5.72, MAX3 alone 5.65
-// (profiles/r06_ab_gemm_nt_split.txt)
-#ifndef SIR_NT_SPLIT_MIX
-#define SIR_NT_SPLIT_MIX 1
-#endif
-#ifndef SIR_NT_P_EPI
-#define SIR_NT_P_EPI 1          // persistent NT epilogue through LDS with whole-row stores (1) or fragment stores (0)
-#endif
+// The hi / lo split is split8_mix and the chunk's row maximum fmax4_mix (2 VGPRs spilled outside the
+// chunk loop), bit-identical to the plain C forms.
 constexpr int NT_P_NMAX = 512;
 
 // GATE: C = sigma'(gate) * (A B^T) (gate [M, N] with C's leading dimension; ReLU: gate > 0 ? x : 0,
@@ -635,7 +499,7 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
             p.d0 = (int64_t)(tt / n_ftiles) * BD;
             p.f0 = (tt % n_ftiles) * BF;
             p.rows = (M - p.d0 < BD) ? (int)(M - p.d0) : BD;
-            p.a = mk_rsrc(A + p.d0 * lda, (SIR_ABL_NT & 1) ? 0u : (uint32_t)(p.rows * lda * 4));
+            p.a = mk_rsrc(A + p.d0 * lda, (uint32_t)(p.rows * lda * 4));
         } else {
             p.d0 = 0;
             p.f0 = 0;
@@ -671,7 +535,7 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
         char* st = lds + buf * STAGE;
         float m = 0.f;
 #pragma unroll
-        for (int i = 0; i < FPT / 4; ++i) m = SIR_NT_MAX3 ? fmax4_mix(m, dv[set][i]) : fmax4(m, dv[set][i]);
+        for (int i = 0; i < FPT / 4; ++i) m = fmax4_mix(m, dv[set][i]);
         m = fmaxf(m, __shfl_xor(m, 1));
         const int se_old = first ? SE_INIT : se_run, se = next_se(se_old, bexp(m));
         se_run = se;
@@ -680,18 +544,7 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
         for (int j = 0; j < FPT; j += 8) {
             const int kl = kp * FPT + j, ks = kl >> 4, pos = kl & 15;
             h8 hv, lv;
-#if SIR_ABL_NT & 4
-            hv = __builtin_bit_cast(h8, dv[set][j / 4]);         // timing-only: no split arithmetic
-            lv = __builtin_bit_cast(h8, dv[set][j / 4 + 1]);
-#else
-#if SIR_NT_SPLIT_MIX == 1
             split8_mix(dv[set][j / 4], dv[set][j / 4 + 1], s, hv, lv);
-#elif SIR_NT_SPLIT_MIX == 2
-            split8_fma(dv[set][j / 4], dv[set][j / 4 + 1], s, hv, lv);
-#else
-            split8(dv[set][j / 4], dv[set][j / 4 + 1], s, hv, lv);
-#endif
-#endif
             *reinterpret_cast<h8*>(st + (0 * 2 + ks) * BD * 32 + fimg(rho, pos >> 3)) = hv;
             *reinterpret_cast<h8*>(st + (1 * 2 + ks) * BD * 32 + fimg(rho, pos >> 3)) = lv;
         }
@@ -725,9 +578,7 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
         const f16v zero = {};
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-#if SIR_NT_P_KSB
             if (ks == 1) __builtin_amdgcn_sched_barrier(0);   // ks 1's fragments not loaded under ks 0's MFMAs
-#endif
             h8 wf[TFT][2], df[TDT][2];
 #pragma unroll
             for (int pt = 0; pt < 2; ++pt) {
@@ -738,14 +589,6 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
                 for (int b = 0; b < TDT; ++b)
                     df[b][pt] = *reinterpret_cast<const h8*>(st + (pt * 2 + ks) * BD * 32 + fimg(d_w + 32 * b + r, h));
             }
-#if SIR_ABL_NT & 8
-#pragma unroll
-            for (int a = 0; a < TFT; ++a)
-#pragma unroll
-                for (int b = 0; b < TDT; ++b)
-                    asm volatile("" :: "v"(wf[a][0]), "v"(wf[a][1]), "v"(df[b][0]), "v"(df[b][1]));   // timing-only
-            continue;
-#endif
 #pragma unroll
             for (int a = 0; a < TFT; ++a)
 #pragma unroll
@@ -770,10 +613,6 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
     // re-derived from an opaque copy of threadIdx.x inside the epilogue: hoisted out of the tile
     // loop, its addresses and offsets would hold VGPRs through every step and force spills
     // (whose reloads, vector-memory ops, drain the load queue).
-#if !SIR_NT_P_EPI
-#error "the fragment-store persistent NT epilogue has no dropout"
-#endif
-#if SIR_NT_P_EPI
     // Epilogue through LDS (stage 1: free after a tile's last step — the next tile's first chunk
     // is in stage 0 — and the 64-row image of pitch BF*4 + 16 is exactly STAGE bytes): per round b
     // every wave writes its 32-row band b, then the block stores whole output rows (one 1-KiB row
@@ -790,7 +629,7 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
         char* const img = lds + STAGE;
         const uint32_t ldc4 = (uint32_t)ldc * 4u;
         const uint32_t nrec = (uint32_t)p.rows * ldc4;
-        const rsrc_t crs = mk_rsrc(C + p.d0 * ldc, (SIR_ABL_NT & 2) ? 0u : nrec);
+        const rsrc_t crs = mk_rsrc(C + p.d0 * ldc, nrec);
         const rsrc_t grs = GATE == 2 ? mk_rsrc(reinterpret_cast<const char*>(gate) + p.d0 * 32, (uint32_t)p.rows * 32u)
                                      : mk_rsrc(GATE ? gate + p.d0 * ldc : C, GATE ? nrec : 0u);
         const float* sc = fin + slot * BD;
@@ -842,7 +681,10 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
                     v.w = __float_as_uint(gate_dact(__uint_as_float(gv.w), __uint_as_float(v.w), gate_relu, gate_slope));
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(v, crs, off, p.f0 * 4, 0);
-                // a 16-byte store reads its data VGPRs over several cycles (see below)
+                // A 16-byte store reads its data VGPRs over several cycles: hipcc (ROCm 7.2) put a
+                // v_pk_mul_f32 overwriting them right after a store with no wait state, and lanes
+                // 12-15 of each 16-lane group stored the new value (measured on MI355X).  Pin the
+                // order and pad the window.
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_nop 1" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
@@ -850,58 +692,7 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
             __syncthreads();
         }
     };
-#else
-    auto epilogue = [&](const TileP& p, int slot) {
-        int tq = threadIdx.x;
-        asm volatile("" : "+v"(tq));
-        const int lq = tq & 63, rq = lq & 31, hq = lq >> 5, wq = tq >> 6;
-        const int d_wq = (wq / WF) * TDT * 32, f_wq = (wq % WF) * TFT * 32;
-        const uint32_t ldc4 = (uint32_t)ldc * 4u;
-        const uint32_t nrec = (uint32_t)p.rows * ldc4;
-        const rsrc_t crs = mk_rsrc(C + p.d0 * ldc, (SIR_ABL_NT & 2) ? 0u : nrec);
-        const float* sc = fin + slot * BD;
-        // < 2^30: row < 256, ldc <= SIR_GEMM_MAX_LD
-        const uint32_t rv = (uint32_t)(d_wq + rq) * ldc4 + (uint32_t)(f_wq + 4 * hq) * 4u;
-#pragma unroll
-        for (int b = 0; b < TDT; ++b) {
-            const float is = sc[d_wq + 32 * b + rq];
-            const uint32_t rb = rv + (uint32_t)(32 * b) * ldc4;
-#pragma unroll
-            for (int a = 0; a < TFT; ++a) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int nc0 = p.f0 + 32 * a + 8 * g;                 // wave-uniform column part
-                    const int n = nc0 + f_wq + 4 * hq;
-                    const float4 it = *reinterpret_cast<const float4*>(inv_l + n);
-                    float4 o;
-                    o.x = acc[a][b][4 * g + 0] * is * it.x;
-                    o.y = acc[a][b][4 * g + 1] * is * it.y;
-                    o.z = acc[a][b][4 * g + 2] * is * it.z;
-                    o.w = acc[a][b][4 * g + 3] * is * it.w;
-                    const float4 bb = *reinterpret_cast<const float4*>(bias_l + n);   // -0 without bias
-                    o.x += bb.x; o.y += bb.y; o.z += bb.z; o.w += bb.w;
-                    u4v ov;
-                    ov.x = __float_as_uint(o.x); ov.y = __float_as_uint(o.y);
-                    ov.z = __float_as_uint(o.z); ov.w = __float_as_uint(o.w);
-                    // columns past N: an offset at the end of the range (dropped)
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, crs, (n < N) ? rb : nrec, nc0 * 4, 0);
-                    // A 16-byte store reads its data VGPRs over several cycles: hipcc (ROCm 7.2) put a
-                    // v_pk_mul_f32 overwriting them right after the store with no wait state, and
-                    // lanes 12-15 of each 16-lane group stored the new value (measured on MI355X).
-                    // Pin the order and pad the window.
-                    __builtin_amdgcn_sched_barrier(0);
-                    asm volatile("s_nop 1" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    };
 
-#endif
-
-#if SIR_NT_PRIO == 2
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
     TileP cur = tile_p(tb), nxt = tile_p(tb + 1);
     load_a(0, cur, 0);
     load_w(cur, 0);
@@ -919,74 +710,40 @@ k_gemm_nt_p(const float* __restrict__ A, int64_t lda, int64_t M, const u4v* __re
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, 2> I2;
-    // LATE (SIR_NT_STAGGER, waves 4-7 = the second wave of every SIMD): split the next chunk
-    // BEFORE the MFMAs of the step instead of after, so that on each SIMD one wave's MFMAs run
-    // beside its partner's split VALU / LDS writes rather than both waves doing the same phase
-    // together (MI355X_MICROARCH.md "Two waves per SIMD" item 9).  Within a step the order is
-    // free: the MFMAs read stage P, the split writes stage P^1, the barrier closes the step.
-    auto step = [&](int c, int j, const TileP& cu, const TileP& nx, auto P_, auto Z_, auto SK_, auto WN_, auto AN_,
-                    auto L_) {
+    // Within a step the MFMAs read stage P, the split writes stage P^1, the barrier closes the step.
+    auto step = [&](int c, int j, const TileP& cu, const TileP& nx, auto P_, auto Z_, auto SK_, auto WN_, auto AN_) {
         constexpr int P = decltype(P_)::value, SK = decltype(SK_)::value;
         constexpr bool Z = decltype(Z_)::value != 0, WN = decltype(WN_)::value != 0, AN = decltype(AN_)::value != 0;
-        constexpr bool LATE = decltype(L_)::value != 0;
         if constexpr (!Z) rescale(P);
-        auto split = [&]() {
-            if constexpr (SK == 2) store(0, 0, true, false, 0);
-            else store(P ^ 1, P ^ 1, false, SK == 1, j & 1);
-        };
-        if constexpr (LATE) split();
-#if SIR_NT_STAGGER == 3
-        const bool late_w = __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256;
-        if (late_w) split();
-#endif
-#if SIR_NT_PRIO == 1
-        __builtin_amdgcn_s_setprio(1);
-#endif
         mfma(P, Z);
-#if SIR_NT_PRIO == 1
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#if SIR_NT_STAGGER == 3
-        if (!late_w) split();
-#else
-        if constexpr (!LATE) split();
-#endif
+        if constexpr (SK == 2) store(0, 0, true, false, 0);
+        else store(P ^ 1, P ^ 1, false, SK == 1, j & 1);
         if constexpr (WN) load_w(nx, c + 2 - NCT);
         else load_w(cu, c + 2);
         if constexpr (AN) load_a(P ^ 1, nx, c + 3 - NCT);
         else load_a(P ^ 1, cu, c + 3);
         __syncthreads();
     };
-    auto run = [&](auto L_) {
+    // the tile loop stays a lambda: written inline, the kernel's scalar registers are allocated differently
+    auto run = [&]() {
         TileP cu = cur, nx = nxt;
         for (int j = 0; tb + j < te; ++j) {
             const TileP nn = tile_p(tb + j + 2);
-            step(0, j, cu, nx, I0(), I1(), I0(), I0(), I0(), L_);
-#if SIR_NT_P_UNROLL
+            step(0, j, cu, nx, I0(), I1(), I0(), I0(), I0());
 #pragma unroll
-#endif
             for (int c = 1; c + 1 <= NCT - 4; c += 2) {
-                step(c, j, cu, nx, I1(), I0(), I0(), I0(), I0(), L_);
-                step(c + 1, j, cu, nx, I0(), I0(), I0(), I0(), I0(), L_);
+                step(c, j, cu, nx, I1(), I0(), I0(), I0(), I0());
+                step(c + 1, j, cu, nx, I0(), I0(), I0(), I0(), I0());
             }
-            step(NCT - 3, j, cu, nx, I1(), I0(), I0(), I0(), I1(), L_);
-            step(NCT - 2, j, cu, nx, I0(), I0(), I1(), I1(), I1(), L_);
-            step(NCT - 1, j, cu, nx, I1(), I0(), I2(), I1(), I1(), L_);
+            step(NCT - 3, j, cu, nx, I1(), I0(), I0(), I0(), I1());
+            step(NCT - 2, j, cu, nx, I0(), I0(), I1(), I1(), I1());
+            step(NCT - 1, j, cu, nx, I1(), I0(), I2(), I1(), I1());
             epilogue(cu, j & 1);
             cu = nx;
             nx = nn;
         }
     };
-#if SIR_NT_STAGGER == 2
-    run(I1());
-#elif SIR_NT_STAGGER == 3
-    run(I0());
-#elif SIR_NT_STAGGER
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) run(I1());
-    else run(I0());
-#else
-    run(I0());
-#endif
+    run();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1039,7 +796,7 @@ k_gemm_tn(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
     const int w = t >> 6, l = t & 63, r = l & 31, h = l >> 5;
     const int m_w = (w / WN) * TMT * 32, n_w = (w % WN) * TNT * 32;
 
-    float4 xv_[SIR_TN_PF][XR / 4];
+    float4 xv_[2][XR / 4];
     // bias gradient of the same linear (column sums of A) rides on the A loads: one partial row
     // per split, written by the blocks of the first n-tile
     const bool do_cs = csum_part != nullptr && is_a;
@@ -1049,30 +806,14 @@ k_gemm_tn(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
         const int64_t vc = v_begin + (int64_t)c * KC;
         const float* src = xbase + vc * ldx;                 // wave-uniform chunk base
         float x[XR];
-#if SIR_TN_PF == 2
         // one branch-free form for every chunk (a load on only one side of a branch makes the
         // compiler's wait counts pessimistic): rows past v_end, and whole chunks past the split,
         // fail the range check and read as 0
         const int64_t nrow = v_end - vc;
-        const rsrc_t rs = mk_rsrc(src, (SIR_ABL_TN || nrow <= 0) ? 0u : (uint32_t)((nrow < KC ? nrow : KC) * ldx * 4));
+        const rsrc_t rs = mk_rsrc(src, nrow <= 0 ? 0u : (uint32_t)((nrow < KC ? nrow : KC) * ldx * 4));
 #pragma unroll
         for (int j = 0; j < XR; ++j)
             x[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, xoff * 4, j * ldx * 4, 0));
-#else
-        if (vc + KC <= v_end) {
-            const rsrc_t rs = mk_rsrc(src, SIR_ABL_TN ? 0u : (uint32_t)(KC * ldx * 4));
-#pragma unroll
-            for (int j = 0; j < XR; ++j)
-                x[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, xoff * 4, j * ldx * 4, 0));
-        } else {   // tail chunk: rows past v_end fail the range check and read as 0
-            const rsrc_t rs = mk_rsrc(src, SIR_ABL_TN ? 0u : (uint32_t)((v_end - vc) * ldx * 4));
-            int o = xoff * 4;
-            asm volatile("" : "+v"(o));      // keep the offsets out of the loop preheader
-#pragma unroll
-            for (int j = 0; j < XR; ++j)
-                x[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, o + j * ldx * 4, 0, 0));
-        }
-#endif
         // no zeroing of columns past Mc / Nc (they re-read column 0): such a column only feeds
         // its own output row / column, which is never stored, under its own scale.  A select
         // here would make the compiler wait for the loads right after issuing them.
@@ -1084,7 +825,7 @@ k_gemm_tn(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
         char* st = lds + buf * STAGE;
         float m = 0.f;
 #pragma unroll
-        for (int j = 0; j < XR / 4; ++j) m = SIR_SPLIT_MIX ? fmax4_mix(m, xv[j]) : fmax4(m, xv[j]);
+        for (int j = 0; j < XR / 4; ++j) m = fmax4_mix(m, xv[j]);
         if (KSPT == 1) m = fmaxf(m, __shfl_xor(m, 1));
         const int se_old = se_run, se = next_se(se_old, bexp(m));
         se_run = se;
@@ -1092,13 +833,8 @@ k_gemm_tn(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
 #pragma unroll
         for (int q = 0; q < KSPT; ++q) {      // k-step kse + q: rows 16q .. 16q+15 of x
             h8 hv[2], lv[2];
-            if constexpr (SIR_SPLIT_MIX) {
-                split8_mix(xv[4 * q + 0], xv[4 * q + 1], s, hv[0], lv[0]);
-                split8_mix(xv[4 * q + 2], xv[4 * q + 3], s, hv[1], lv[1]);
-            } else {
-                split8(xv[4 * q + 0], xv[4 * q + 1], s, hv[0], lv[0]);
-                split8(xv[4 * q + 2], xv[4 * q + 3], s, hv[1], lv[1]);
-            }
+            split8_mix(xv[4 * q + 0], xv[4 * q + 1], s, hv[0], lv[0]);
+            split8_mix(xv[4 * q + 2], xv[4 * q + 3], s, hv[1], lv[1]);
             char* hd = st + hi_off + q * rows_img * 32;    // fimg(cl, 1) = fimg(cl, 0) + 512
             *reinterpret_cast<h8*>(hd) = hv[0];
             *reinterpret_cast<h8*>(hd + 512) = hv[1];
@@ -1176,7 +912,6 @@ k_gemm_tn(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
     };
 
     if (t < 2) rescaled[t] = -1;
-#if SIR_TN_PF == 2
     // two chunks in flight: step c multiplies chunk c (stage c&1) while chunks c+1 (set (c+1)&1)
     // and c+2 (set c&1, issued at the top of the step) load; chunks past the split load as zeros
     // (empty range), so every step issues the same loads and the wait counts stay exact.
@@ -1198,20 +933,6 @@ k_gemm_tn(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
         step(c + 1, 1);
     }
     if (c < nc) step(c, 0);
-#else
-    if (nc > 0) {
-        load(0, 0);
-        store(0, 0, 0, true);
-    }
-    __syncthreads();
-    for (int c = 0; c < nc; ++c) {
-        const bool more = c + 1 < nc;
-        if (more) load(0, c + 1);
-        compute(c);
-        if (more) store(0, (c & 1) ^ 1, c + 1);
-        __syncthreads();
-    }
-#endif
 
     // epilogue: part[p][m][n] = acc * 2^-se_a(m) * 2^-se_b(n)
     float* sc = reinterpret_cast<float*>(lds);
@@ -2073,6 +1794,28 @@ hipError_t run_gemm_pack(const float* W, int64_t ldw, int N, int K, int trans, v
     return hipGetLastError();
 }
 
+// k_gemm_nt_p<kc, GATE> over C's 256 x 256 tiles, a contiguous range of them per block and one block
+// per CU (kc = K / KC: 4, 8 or 16); false, with nothing launched, if the tile count is out of range
+template <int GATE>
+static bool launch_gemm_nt_p(const float* A, int64_t lda, int64_t M, int kc, const void* packed, int N,
+                             const float* bias, float* C, int64_t ldc, hipStream_t st, const Drop& drop,
+                             const float* gate, int gate_relu, float gate_slope) {
+    const int np = (int)gemm_pack_npad(N);
+    const u4v* wp = static_cast<const u4v*>(packed);
+    const float* inv = reinterpret_cast<const float*>(static_cast<const char*>(packed) + (int64_t)kc * 4 * np * 32);
+    constexpr int BD = 256, BF = 256;
+    const int nft = (N + BF - 1) / BF;
+    const int64_t ntiles = (M + BD - 1) / BD * nft;
+    const int ncu = device_cu_count();
+    if (ntiles >= (int64_t)1 << 30) return false;
+    const int tpb = (int)((ntiles + ncu - 1) / ncu);
+    const int nblk = (int)((ntiles + tpb - 1) / tpb);
+    auto kern = kc == 4 ? k_gemm_nt_p<4, GATE> : (kc == 8 ? k_gemm_nt_p<8, GATE> : k_gemm_nt_p<16, GATE>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, st, A, lda, M, wp, np, inv, bias, N, C, ldc, nft,
+                       (int)ntiles, tpb, drop, gate, gate_relu, gate_slope);
+    return true;
+}
+
 hipError_t run_gemm_nt(const float* A, int64_t lda, int64_t M, int K, const void* packed, int N,
                        const float* bias, float* C, int64_t ldc, hipStream_t st, const Drop& drop, const float* gate,
                        int gate_relu, float gate_slope, const uint64_t* gate_mask) {
@@ -2081,27 +1824,12 @@ hipError_t run_gemm_nt(const float* A, int64_t lda, int64_t M, int K, const void
     if (gate != nullptr || gate_mask != nullptr) {   // fused in k_gemm_nt_p's epilogue; other routes: afterwards
         const int np = (int)gemm_pack_npad(N), kc = (K + KC - 1) / KC;
         if (M >= gemm_small_rows() && N > 128 && np <= NT_P_NMAX && K % KC == 0 && (kc == 4 || kc == 8 || kc == 16)) {
-            const u4v* wp = static_cast<const u4v*>(packed);
-            const float* inv = reinterpret_cast<const float*>(static_cast<const char*>(packed) + (int64_t)kc * 4 * np * 32);
-            constexpr int BD = 256, BF = 256;
-            const int nft = (N + BF - 1) / BF;
-            const int64_t ntiles = (M + BD - 1) / BD * nft;
-            const int ncu = device_cu_count();
-            if (ntiles < (int64_t)1 << 30) {
-                const int tpb = (int)((ntiles + ncu - 1) / ncu);
-                const int nblk = (int)((ntiles + tpb - 1) / tpb);
-                if (gate_mask != nullptr) {
-                    auto kern = kc == 4 ? k_gemm_nt_p<4, 2> : (kc == 8 ? k_gemm_nt_p<8, 2> : k_gemm_nt_p<16, 2>);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, st, A, lda, M, wp, np, inv, bias, N, C,
-                                       ldc, nft, (int)ntiles, tpb, drop, reinterpret_cast<const float*>(gate_mask),
-                                       gate_relu, gate_slope);
-                } else {
-                    auto kern = kc == 4 ? k_gemm_nt_p<4, 1> : (kc == 8 ? k_gemm_nt_p<8, 1> : k_gemm_nt_p<16, 1>);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, st, A, lda, M, wp, np, inv, bias, N, C,
-                                       ldc, nft, (int)ntiles, tpb, drop, gate, gate_relu, gate_slope);
-                }
-                return hipGetLastError();
-            }
+            const bool done =
+                gate_mask != nullptr
+                    ? launch_gemm_nt_p<2>(A, lda, M, kc, packed, N, bias, C, ldc, st, drop,
+                                          reinterpret_cast<const float*>(gate_mask), gate_relu, gate_slope)
+                    : launch_gemm_nt_p<1>(A, lda, M, kc, packed, N, bias, C, ldc, st, drop, gate, gate_relu, gate_slope);
+            if (done) return hipGetLastError();
         }
         hipError_t err = run_gemm_nt(A, lda, M, K, packed, N, bias, C, ldc, st, drop, nullptr, 0, 0.f, nullptr);
         if (err != hipSuccess) return err;
@@ -2119,20 +1847,9 @@ hipError_t run_gemm_nt(const float* A, int64_t lda, int64_t M, int K, const void
     const float* inv = reinterpret_cast<const float*>(static_cast<const char*>(packed) + (int64_t)kc * 4 * np * 32);
     const bool kfull = K % KC == 0;
     if (M < gemm_small_rows()) return run_gemm_nt_s(A, lda, M, K, packed, N, bias, C, ldc, st, drop);
-    if (SIR_NT_PERSIST && N > 128 && np <= NT_P_NMAX && kfull && (kc == 4 || kc == 8 || kc == 16)) {
-        constexpr int BD = 256, BF = 256;
-        const int nft = (N + BF - 1) / BF;
-        const int64_t ntiles = (M + BD - 1) / BD * nft;
-        const int ncu = device_cu_count();
-        if (ntiles < (int64_t)1 << 30) {
-            const int tpb = (int)((ntiles + ncu - 1) / ncu);
-            const int nblk = (int)((ntiles + tpb - 1) / tpb);
-            auto kern = kc == 4 ? k_gemm_nt_p<4, 0> : (kc == 8 ? k_gemm_nt_p<8, 0> : k_gemm_nt_p<16, 0>);
-            hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, st, A, lda, M, wp, np, inv, bias, N, C, ldc,
-                               nft, (int)ntiles, tpb, drop, nullptr, 0, 0.f);
-            return hipGetLastError();
-        }
-    }
+    if (N > 128 && np <= NT_P_NMAX && kfull && (kc == 4 || kc == 8 || kc == 16) &&
+        launch_gemm_nt_p<0>(A, lda, M, kc, packed, N, bias, C, ldc, st, drop, nullptr, 0, 0.f))
+        return hipGetLastError();
     if (N > 128) {
         constexpr int BD = 256, BF = 256;
         const int nft = (N + BF - 1) / BF;
@@ -2241,14 +1958,9 @@ hipError_t run_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb,
         hipLaunchKernelGGL(k_gemm_tn_s, dim3((unsigned)((int64_t)P * smt * snt)), dim3(256), 0, st, A, lda, B, ldb, R,
                            Mc, Nc, part, cpart, smt, snt, rps);
     } else
-#if SIR_TN_CFG == 2
     // 8 waves (2 per SIMD, 256 registers), 128x64 per wave, a thread loads a whole column chunk
     hipLaunchKernelGGL((k_gemm_tn<2, 4, 4, 2>), dim3((unsigned)(P * nmt * nnt)), dim3(512), 0, st,
                        A, lda, B, ldb, R, Mc, Nc, part, cpart, nmt, nnt, rps);
-#else
-    hipLaunchKernelGGL((k_gemm_tn<4, 4, 2, 2>), dim3((unsigned)(P * nmt * nnt)), dim3(1024), 0, st,
-                       A, lda, B, ldb, R, Mc, Nc, part, cpart, nmt, nnt, rps);
-#endif
     // C = sum_p part[p] and colsum = sum_p cpart[p], in split order, one launch
     const int64_t count = (int64_t)Mc * Nc;
     const int64_t nbm = (count + 255) / 256, nbc = colsum != nullptr ? (Mc + 255) / 256 : 0;

@@ -242,12 +242,6 @@ k_gemm_tn16(const unsigned short* __restrict__ A, int64_t lda, const unsigned sh
 // Chunks of KC k-values: a thread loads half of one row's chunk (KC/2 values) and the same
 // number of packed weight bytes into a register set, two sets alternate (two chunks in flight
 // while one is multiplied out of LDS), and the pipeline runs on across tile boundaries.
-#ifndef SIR_NT16_EPI
-#define SIR_NT16_EPI 1          // 16-bit NT epilogue through LDS with whole-row stores (1) or fragment stores (0)
-#endif
-#ifndef SIR_NT16_ABL
-#define SIR_NT16_ABL 0          // timing-only ablations: 1 = A loads dropped, 2 = C stores dropped, 4 = no MFMAs
-#endif
 
 template <int I, int N_, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -287,7 +281,7 @@ k_gemm_nt16(const void* __restrict__ A, int64_t lda, int64_t M, const u4v* __res
     static_assert(NS >= 2 && NS <= NC && NC % NS == 0, "register sets: a tile's chunks map to sets the same way");
     constexpr int IMG_ROWS = 32 * WD;                 // epilogue image: one 32-row band per data wave
     constexpr int EPITCH = BFT * EC + 16;             // epilogue image row pitch (bytes)
-    constexpr int EPI_BYTES = SIR_NT16_EPI ? IMG_ROWS * EPITCH : 0;
+    constexpr int EPI_BYTES = IMG_ROWS * EPITCH;
     __shared__ __attribute__((aligned(16))) char lds[2 * STAGE + 512 * 4 + EPI_BYTES];
     float* const bias_l = reinterpret_cast<float*>(lds + 2 * STAGE);
     char* const epi = lds + 2 * STAGE + 512 * 4;
@@ -311,7 +305,7 @@ k_gemm_nt16(const void* __restrict__ A, int64_t lda, int64_t M, const u4v* __res
             p.d0 = (int64_t)(tt / n_ftiles) * BD;
             p.f0 = (tt % n_ftiles) * BFT;
             p.rows = (M - p.d0 < BD) ? (int)(M - p.d0) : BD;
-            p.a = mk_rsrc(static_cast<const char*>(A) + p.d0 * lda * EA, (SIR_NT16_ABL & 1) ? 0u : (uint32_t)(p.rows * lda * EA));
+            p.a = mk_rsrc(static_cast<const char*>(A) + p.d0 * lda * EA, (uint32_t)(p.rows * lda * EA));
             p.cp = mk_rsrc(Acopy + p.d0 * ldac, (Acopy != nullptr && p.f0 == 0) ? (uint32_t)(p.rows * ldac * 2) : 0u);
         } else {
             p.d0 = 0;
@@ -376,30 +370,16 @@ k_gemm_nt16(const void* __restrict__ A, int64_t lda, int64_t M, const u4v* __res
 #pragma unroll
             for (int b = 0; b < TDT; ++b)
                 df[b] = *reinterpret_cast<const u4v*>(st + ks * PLANE + fimg(d_w + 32 * b + r, h));
-#if SIR_NT16_ABL & 4
-#pragma unroll
-            for (int a = 0; a < TFT; ++a)
-#pragma unroll
-                for (int b = 0; b < TDT; ++b) {
-                    asm volatile("" :: "v"(wf[a]), "v"(df[b]));      // timing-only: no MFMAs
-                    if (zinit && ks == 0) acc[a][b] = zero;
-                }
-#else
 #pragma unroll
             for (int a = 0; a < TFT; ++a)
 #pragma unroll
                 for (int b = 0; b < TDT; ++b)
                     acc[a][b] = mfma16<BF>(wf[a], df[b], (zinit && ks == 0) ? zero : acc[a][b]);
-#endif
         }
     };
     // C[m][n] = acc + bias[n]; rows past M fall outside the store's range, columns past N are
     // sent past its end (dropped).  Lane indices re-derived from an opaque threadIdx copy so that
     // they do not hold VGPRs through the steps.
-#if !SIR_NT16_EPI
-#error "the fragment-store 16-bit NT epilogue has no dropout"
-#endif
-#if SIR_NT16_EPI
     // Epilogue through LDS: per round b, every wave writes its 32-row band b (bias added, rounded
     // to the output type) into a row-major image of 64 tile rows, then the block stores whole
     // output rows — each wave-instruction writes 1 KiB of contiguous row bytes (2 bf16 / 1 fp32
@@ -412,7 +392,7 @@ k_gemm_nt16(const void* __restrict__ A, int64_t lda, int64_t M, const u4v* __res
         const int f_wq = (wq % WF) * TFT * 32;
         const uint32_t ldcb = (uint32_t)ldc * EC;
         const uint32_t nrec = (uint32_t)p.rows * ldcb;
-        const rsrc_t crs = mk_rsrc(static_cast<char*>(C) + p.d0 * ldc * EC, (SIR_NT16_ABL & 2) ? 0u : nrec);
+        const rsrc_t crs = mk_rsrc(static_cast<char*>(C) + p.d0 * ldc * EC, nrec);
         char* const wrow = epi + ((wq / WF) * 32 + rq) * EPITCH + (f_wq + 4 * hq) * EC;
 #pragma unroll
         for (int b = 0; b < TDT; ++b) {
@@ -466,52 +446,6 @@ k_gemm_nt16(const void* __restrict__ A, int64_t lda, int64_t M, const u4v* __res
             __syncthreads();
         }
     };
-#else
-    auto epilogue = [&](const TileP& p) {
-        int tq = threadIdx.x;
-        asm volatile("" : "+v"(tq));
-        const int lq = tq & 63, rq = lq & 31, hq = lq >> 5, wq = tq >> 6;
-        const int d_wq = (wq / WF) * TDT * 32, f_wq = (wq % WF) * TFT * 32;
-        const uint32_t ldcb = (uint32_t)ldc * EC;
-        const uint32_t nrec = (uint32_t)p.rows * ldcb;
-        const rsrc_t crs = mk_rsrc(static_cast<char*>(C) + p.d0 * ldc * EC, (SIR_NT16_ABL & 2) ? 0u : nrec);
-        const uint32_t rv = (uint32_t)(d_wq + rq) * ldcb + (uint32_t)(f_wq + 4 * hq) * EC;
-#pragma unroll
-        for (int b = 0; b < TDT; ++b) {
-            const uint32_t rb = rv + (uint32_t)(32 * b) * ldcb;
-#pragma unroll
-            for (int a = 0; a < TFT; ++a) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int nc0 = p.f0 + 32 * a + 8 * g;
-                    const int n = nc0 + f_wq + 4 * hq;
-                    const float4 bb = *reinterpret_cast<const float4*>(bias_l + n);
-                    const float o0 = acc[a][b][4 * g + 0] + bb.x, o1 = acc[a][b][4 * g + 1] + bb.y;
-                    const float o2 = acc[a][b][4 * g + 2] + bb.z, o3 = acc[a][b][4 * g + 3] + bb.w;
-                    const uint32_t off = (n < N) ? rb : nrec;
-                    if constexpr (C32) {
-                        u4v ov;
-                        ov.x = __float_as_uint(o0); ov.y = __float_as_uint(o1);
-                        ov.z = __float_as_uint(o2); ov.w = __float_as_uint(o3);
-                        __builtin_amdgcn_raw_buffer_store_b128(ov, crs, off, nc0 * EC, 0);
-                    } else {
-                        typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-                        u2v ov;
-                        ov.x = pack2(o0, o1, BF);
-                        ov.y = pack2(o2, o3, BF);
-                        __builtin_amdgcn_raw_buffer_store_b64(ov, crs, off, nc0 * EC, 0);
-                    }
-                    // the store reads its data VGPRs over several cycles: keep the next writes of
-                    // them away (see k_gemm_nt_p's epilogue)
-                    __builtin_amdgcn_sched_barrier(0);
-                    asm volatile("s_nop 1" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    };
-
-#endif
 
     // step c: chunk c is multiplied out of LDS buffer c & 1, chunks c+1 .. c+NS are in flight in
     // register sets (c+1) % NS .. c % NS; chunk c+NS is issued into set c % NS (chunk c's, already

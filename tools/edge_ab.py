@@ -2,8 +2,8 @@
 """A/B the edge passes of several builds of libsirconv (same C ABI, different compile flags) on
 identical data, interleaved in ONE process (cdna_hip_programming.md §5.4 rule 24).
 
-    make -C sir-gcn_amd/csrc VARIANT=nt DEFS=-DSIR_NT_STREAM=1
-    python tools/edge_ab.py --graph S2 --libs base=sir-gcn_amd/lib/libsirconv.so nt=sir-gcn_amd/lib/libsirconv_nt.so
+    make -C sir-gcn_amd/csrc VARIANT=u8 DEFS=-DSIR_UNROLL_FWD=8
+    python tools/edge_ab.py --graph S2 --libs base=sir-gcn_amd/lib/libsirconv.so u8=sir-gcn_amd/lib/libsirconv_u8.so
 """
 import argparse
 import ctypes

@@ -2,8 +2,8 @@
 """A/B the projection GEMMs of several builds of libsirconv (same C ABI, different compile
 flags) on the layer's shapes, interleaved in ONE process (cdna_hip_programming.md §5.4 rule 24).
 
-    make -C sir-gcn_amd/csrc VARIANT=nt2 DEFS=-DSIR_NT_CFG=2
-    python tools/gemm_ab.py --libs base=sir-gcn_amd/lib/libsirconv.so nt2=sir-gcn_amd/lib/libsirconv_nt2.so
+    make -C sir-gcn_amd/csrc VARIANT=mr2k DEFS=-DSIR_TN_MINROWS=2048
+    python tools/gemm_ab.py --libs base=sir-gcn_amd/lib/libsirconv.so mr2k=sir-gcn_amd/lib/libsirconv_mr2k.so
 Prints ms (median over rounds) per shape and library, and checks the outputs agree (bitwise
 equality is not expected across tilings; the relative difference is printed)."""
 import argparse

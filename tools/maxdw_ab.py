@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the max backward's dW_R / db_R kernels (sir_max_dw_qk: SIR_MAXDW=1 k_max_dw_qk, 4-row / 64-edge
-batches; 2 k_max_dw_qk2, 16-row / 128-edge batches) on an S1-shaped max layer (V=500k, E=10M, H=O=256,
-LeakyReLU 0.2), interleaved in one process; the outputs must be bit-identical."""
+"""A/B of the max backward's dW_R / db_R kernel (sir_max_dw_qk: k_max_dw_qk2, 16-row / 128-edge batches) in
+several builds of libsirconv on an S1-shaped max layer (V=500k, E=10M, H=O=256, LeakyReLU 0.2), interleaved
+in one process; the outputs must be bit-identical."""
 import argparse
 import ctypes
 import os
@@ -23,7 +23,6 @@ def main():
     ap.add_argument("--V", type=int, default=500_000)
     ap.add_argument("--E", type=int, default=10_000_000)
     ap.add_argument("--H", type=int, default=256)
-    ap.add_argument("--forms", default="1,2", help="SIR_MAXDW values, each optionally @<lib name>")
     ap.add_argument("--libs", nargs="*", default=[], help="name=path of A/B library builds (same ABI)")
     a = ap.parse_args()
     _native.load()
@@ -41,7 +40,6 @@ def main():
     arg = torch.empty(a.V, a.H, device=dev, dtype=torch.int32)
     edgemlp._fwd(plan, Q, K, W, b, "max", _native.ACT_LEAKY, 0.2, _native.ACT_IDENTITY, Y, arg)
     dY = torch.randn(a.V, a.H, device=dev)
-    forms = a.forms.split(",")
     libs = {"main": _native.load()}
     for kv in a.libs:
         name, path = kv.split("=", 1)
@@ -51,12 +49,11 @@ def main():
             if f is not None:
                 f.restype, f.argtypes = res, args
         libs[name] = h
+    forms = list(libs)
     outs, times = {}, {f: [] for f in forms}
     for r in range(a.rounds):
         for f in forms:
-            form, _, lib = f.partition("@")
-            os.environ["SIR_MAXDW"] = form
-            _native._lib = libs[lib or "main"]
+            _native._lib = libs[f]
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             dW, db = _native.max_dw_qk(plan.dst, arg, dY, Q, K, a.H, _native.ACT_LEAKY, 0.2)
@@ -67,7 +64,7 @@ def main():
             outs[f] = (dW, db)
     for f in forms:
         same = torch.equal(outs[f][0], outs[forms[0]][0]) and torch.equal(outs[f][1], outs[forms[0]][1])
-        print(f"SIR_MAXDW={f}: {statistics.median(times[f]):.3f} ms (min {min(times[f]):.3f}), "
+        print(f"{f}: {statistics.median(times[f]):.3f} ms (min {min(times[f]):.3f}), "
               f"bit-identical to {forms[0]}: {same}", flush=True)
 
 

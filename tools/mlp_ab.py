@@ -3,8 +3,7 @@
 Sequential sigma's sum) of several builds of libsirconv, interleaved in ONE process, on a named
 graph; checks every build's output (and max arg) is bit-identical to the first.
 
-    make -C sir-gcn_amd/csrc VARIANT=mlpold DEFS=-DSIR_MLP_PIPE=0
-    python tools/mlp_ab.py --graph S1 --libs new=sir-gcn_amd/lib/libsirconv.so old=sir-gcn_amd/lib/libsirconv_mlpold.so
+    python tools/mlp_ab.py --graph S1 --libs new=sir-gcn_amd/lib/libsirconv.so old=<library of another build>
 """
 import argparse
 import os

@@ -44,6 +44,30 @@
  *  - `col` (and `perm_s`) may be NULL when the graph has no edges.
  *  - Return 0 on success, otherwise an SIR_E* code; sir_last_error() gives the text
  *    (thread-local).
+ *  - Non-finite values (tests/test_poison_gpu.py holds the kernels to this).
+ *    Isolation: a result depends on the logical operands only.  The columns [N, ld) of a row, rows past
+ *    the last, the rows of a node matrix or an edge table that no edge of the call references (Q[v], G[v]
+ *    of a row without edges, K[u] of a node without out-edges, unreferenced rows of Eh), every workspace
+ *    and the previous content of an output may hold anything, NaN included; nothing outside the logical
+ *    output (and the workspace up to its queried size) is written.  A zero weight is applied by
+ *    selection, never by a multiply.
+ *    Propagation: an Inf or NaN the result does depend on is never turned into a finite number.  The
+ *    kernels that select, add and scale by a finite factor (edge passes, edge-feature kernels, the
+ *    edge-materialised helpers, resid-act, readout sum / mean, column sums) return the class IEEE
+ *    arithmetic gives (NaN, +Inf, -Inf; ReLU(-Inf) = 0, LeakyReLU(-Inf) = -Inf, Inf - Inf = NaN).
+ *    Maximum (sir_segment_max, the edge-MLP max forward in every form, sir_graph_pool_fwd max):
+ *    torch.max's order — a NaN beats every number — with the first of equal candidates, and the first
+ *    NaN, as arg; a row with edges always returns one of its edges (all -Inf: -Inf and the first edge),
+ *    only a row without edges returns 0 / -1.  The rule does not depend on the plan's chunk, the
+ *    route, or the readout's slab cut.
+ *    Deviations from torch: (1) a dropped element of the feature dropout is 0 whatever it held
+ *    (nn.Dropout gives NaN * 0 = NaN); a kept one propagates.  (2) sigma'(z) of the ReLU family at a
+ *    NaN z is the "z > 0 is false" branch (0 for ReLU, slope for LeakyReLU), where torch's
+ *    threshold_backward passes the gradient; rows such an edge does not touch are unaffected.  (3) The
+ *    GEMMs and the edge MLP scale a row by a power of two taken from its largest magnitude, and the norms
+ *    go through a variance: a row / column holding Inf may come out NaN where the reference keeps +-Inf;
+ *    it is non-finite in exactly the rows / columns the reference marks, and a non-finite value in one
+ *    data row never reaches another row.
  */
 #ifndef SIRCONV_H
 #define SIRCONV_H

@@ -32,7 +32,7 @@ __device__ __forceinline__ float sig(float z, float slope) {
     if constexpr (ACT == ACT_IDENTITY) {
         return z;
     } else if constexpr (ACT == ACT_RELU) {
-        return z > 0.f ? z : 0.f;
+        return z <= 0.f ? 0.f : z;       // not z > 0 ? z : 0: ReLU(NaN) is NaN (torch.relu), never 0
     } else if constexpr (ACT == ACT_LEAKY) {
         return z > 0.f ? z : z * slope;
     } else if constexpr (ACT == ACT_GELU) {

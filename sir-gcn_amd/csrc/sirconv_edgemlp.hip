@@ -196,7 +196,7 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
     int bidx[TPW];
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
-        racc[j] = 0.f; best[j] = -INFINITY; bidx[j] = INT_MAX;
+        racc[j] = 0.f; best[j] = -INFINITY; bidx[j] = MAX_NONE;
         const int n = 32 * (w + NW * j) + (l & 31);
         bb[j] = (bias != nullptr && n < F) ? round_st<ST>(bias[n]) : 0.f;
         iw[j] = (n < F) ? winv[n] : 0.f;
@@ -322,7 +322,7 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
                 if (i < nv) {
                     const float m = act_f<ACT2>(acc[j][r] * sInv[i] * iw[j] + bb[j], slope);
                     if constexpr (RED == 3) {
-                        if (m > best[j]) { best[j] = m; bidx[j] = t0 + i; }    // strict >: first wins
+                        if (max_beats(m, best[j])) { best[j] = m; bidx[j] = t0 + i; }    // first wins
                     } else {
                         racc[j] += sC[i] * m;
                     }
@@ -338,15 +338,15 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
         if constexpr (RED == 3) {
             const float ob = __shfl_xor(best[j], 32);
             const int oi = __shfl_xor(bidx[j], 32);
-            if (ob > best[j] || (ob == best[j] && oi < bidx[j])) { best[j] = ob; bidx[j] = oi; }
+            if (max_merges(ob, oi, best[j], bidx[j])) { best[j] = ob; bidx[j] = oi; }
             if (l < 32 && n < F) {
-                const bool any = bidx[j] != INT_MAX;
+                const int ba = max_arg(bidx[j], e0, e1);
                 if (slot < 0) {
-                    out[(int64_t)row * ldo + n] = any ? best[j] : 0.f;
-                    arg[(int64_t)row * lda + n] = any ? bidx[j] : -1;
+                    out[(int64_t)row * ldo + n] = e1 > e0 ? best[j] : 0.f;
+                    arg[(int64_t)row * lda + n] = ba;
                 } else {
                     pval[(int64_t)slot * F + n] = best[j];
-                    parg[(int64_t)slot * F + n] = bidx[j];
+                    parg[(int64_t)slot * F + n] = ba;
                 }
             }
         } else {
@@ -411,7 +411,7 @@ k_mlp_fwd16p(const int* __restrict__ rowptr, const int* __restrict__ col, const 
         const int k4 = 4 * l;
         const float4 q4 = (k4 < H) ? *reinterpret_cast<const float4*>(qp + k4) : make_float4(0.f, 0.f, 0.f, 0.f);
         float racc = 0.f, best = -INFINITY;
-        int bidx = INT_MAX;
+        int bidx = MAX_NONE;
         for (int t0 = e0; t0 < e1; t0 += 32) {
             const int nv = (e1 - t0) < 32 ? (e1 - t0) : 32;
             float4 kv[RPW];
@@ -472,7 +472,7 @@ k_mlp_fwd16p(const int* __restrict__ rowptr, const int* __restrict__ col, const 
                     if (i < nv) {
                         const float m = act_f<ACT2>(acc[r] * sInv[i] * iwv + bbv, slope);
                         if constexpr (RED == 3) {
-                            if (m > best) { best = m; bidx = t0 + i; }    // strict >: first wins
+                            if (max_beats(m, best)) { best = m; bidx = t0 + i; }    // first wins
                         } else {
                             racc += sC[i] * m;
                         }
@@ -485,15 +485,15 @@ k_mlp_fwd16p(const int* __restrict__ rowptr, const int* __restrict__ col, const 
             if constexpr (RED == 3) {
                 const float ob = __shfl_xor(best, 32);
                 const int oi = __shfl_xor(bidx, 32);
-                if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+                if (max_merges(ob, oi, best, bidx)) { best = ob; bidx = oi; }
                 if (l < 32 && n < F) {
-                    const bool any = bidx != INT_MAX;
+                    const int ba = max_arg(bidx, e0, e1);
                     if (slot < 0) {
-                        out[(int64_t)row * ldo + n] = any ? best : 0.f;
-                        arg[(int64_t)row * lda + n] = any ? bidx : -1;
+                        out[(int64_t)row * ldo + n] = e1 > e0 ? best : 0.f;
+                        arg[(int64_t)row * lda + n] = ba;
                     } else {
                         pval[(int64_t)slot * F + n] = best;
-                        parg[(int64_t)slot * F + n] = bidx;
+                        parg[(int64_t)slot * F + n] = ba;
                     }
                 }
             } else {
@@ -669,7 +669,7 @@ k_mlp_fwd16q(const int* __restrict__ col, const int4* __restrict__ items, int64_
     gather(n1, colv_n1);
     __syncthreads();
     float racc = 0.f, best = -INFINITY;
-    int bidx = INT_MAX;
+    int bidx = MAX_NONE;
     int bf = 0;
     while (cur.itx < n_items) {
         const int nv = (cur.e1 - cur.t0) < 32 ? (cur.e1 - cur.t0) : 32;
@@ -708,7 +708,7 @@ k_mlp_fwd16q(const int* __restrict__ col, const int4* __restrict__ items, int64_
                 const float iv = r % 4 == 0 ? inv4[r / 4].x : r % 4 == 1 ? inv4[r / 4].y : r % 4 == 2 ? inv4[r / 4].z : inv4[r / 4].w;
                 const float m = act_f<ACT2>(acc[r] * iv * iwv + bbv, slope);
                 if constexpr (RED == 3) {
-                    const bool take = i < nv && m > best;         // strict >: first wins
+                    const bool take = i < nv && max_beats(m, best);         // first wins
                     best = take ? m : best;
                     bidx = take ? cur.t0 + i : bidx;
                 } else {
@@ -721,15 +721,15 @@ k_mlp_fwd16q(const int* __restrict__ col, const int4* __restrict__ items, int64_
                 if constexpr (RED == 3) {
                     const float ob = __shfl_xor(best, 32);
                     const int oi = __shfl_xor(bidx, 32);
-                    if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+                    if (max_merges(ob, oi, best, bidx)) { best = ob; bidx = oi; }
                     if (l < 32 && n < F) {
-                        const bool any = bidx != INT_MAX;
+                        const int ba = max_arg(bidx, cur.e0, cur.e1);
                         if (slot < 0) {
-                            out[(int64_t)row * ldo + n] = any ? best : 0.f;
-                            arg[(int64_t)row * lda + n] = any ? bidx : -1;
+                            out[(int64_t)row * ldo + n] = cur.e1 > cur.e0 ? best : 0.f;
+                            arg[(int64_t)row * lda + n] = ba;
                         } else {
                             pval[(int64_t)slot * F + n] = best;
-                            parg[(int64_t)slot * F + n] = bidx;
+                            parg[(int64_t)slot * F + n] = ba;
                         }
                     }
                 } else {
@@ -749,7 +749,7 @@ k_mlp_fwd16q(const int* __restrict__ col, const int4* __restrict__ items, int64_
                 }
                 racc = 0.f;
                 best = -INFINITY;
-                bidx = INT_MAX;
+                bidx = MAX_NONE;
             }
         }
         __syncthreads();
@@ -891,7 +891,7 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
     gather(colv1, rowv1);
     __syncthreads();
     float racc = 0.f, best = -INFINITY;
-    int bidx = INT_MAX;
+    int bidx = MAX_NONE;
     bool first_run = true;
     int bf = 0;
     float* const mw = mt[w];
@@ -960,15 +960,15 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
                 const uint32_t bh = bnd >> (16 * h);
                 const int eb = (int)t0 + 16 * h;
                 float hb_ = h ? -INFINITY : best;
-                int hi_ = h ? INT_MAX : bidx;
+                int hi_ = h ? MAX_NONE : bidx;
                 float pb = -INFINITY;                 // half 1: its first run, held back
-                int pi = INT_MAX, pr = 0;
+                int pi = MAX_NONE, pr = 0;
                 bool seen = false;
                 const bool fo_n = n < F;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const float v = mh[i];
-                    const bool take = v > hb_;
+                    const bool take = max_beats(v, hb_);
                     hb_ = take ? v : hb_;
                     hi_ = take ? eb + i : hi_;
                     // the rows of edges i and 16 + i by readlane (read whatever the EXEC mask: a cross-lane
@@ -980,26 +980,24 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
                         if (h == 1 && !seen) {
                             pb = hb_; pi = hi_; pr = re;
                         } else if (fo_n) {
-                            const bool any = hi_ != INT_MAX;
-                            out[(int64_t)re * ldo + n] = any ? hb_ : 0.f;
-                            arg[(int64_t)re * lda + n] = any ? hi_ : -1;
+                            out[(int64_t)re * ldo + n] = hb_;
+                            arg[(int64_t)re * lda + n] = hi_ != MAX_NONE ? hi_ : rowptr[re];
                         }
                         seen = true;
                         hb_ = -INFINITY;
-                        hi_ = INT_MAX;
+                        hi_ = MAX_NONE;
                     }
                 }
                 // half 0's trailing state <-> half 1's
                 const float ob = __shfl_xor(hb_, 32);
                 const int oi = __shfl_xor(hi_, 32);
                 if (h == 1 && (bh & 0xffffu) != 0u) {                 // half 1 had a run end: its first
-                    const bool t1 = pb > ob;                         // run continues half 0's trailing one
+                    const bool t1 = max_beats(pb, ob);               // run continues half 0's trailing one
                     const float mb = t1 ? pb : ob;
                     const int mi = t1 ? pi : oi;
                     if (fo_n) {
-                        const bool any = mi != INT_MAX;
-                        out[(int64_t)pr * ldo + n] = any ? mb : 0.f;
-                        arg[(int64_t)pr * lda + n] = any ? mi : -1;
+                        out[(int64_t)pr * ldo + n] = mb;
+                        arg[(int64_t)pr * lda + n] = mi != MAX_NONE ? mi : rowptr[pr];
                     }
                 }
                 // the carry into the next tile (both halves): half 1's trailing run, or, without a run end
@@ -1007,7 +1005,7 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
                 const float b0 = h ? ob : hb_, b1 = h ? hb_ : ob;
                 const int i0 = h ? oi : hi_, i1 = h ? hi_ : oi;
                 const bool end1 = (bnd >> 16) != 0u;
-                const bool t1 = end1 || b1 > b0;
+                const bool t1 = end1 || max_beats(b1, b0);
                 best = t1 ? b1 : b0;
                 bidx = t1 ? i1 : i0;
                 goto tile_done;
@@ -1026,7 +1024,7 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
             if (e < nv) {
                 const float v = mv[e];
                 if constexpr (RED == 3) {
-                    const bool take = v > best;           // strict >: the first arg-max edge wins
+                    const bool take = max_beats(v, best);           // the first arg-max edge wins
                     best = take ? v : best;
                     bidx = take ? (int)(t0 + e) : bidx;
                 } else {
@@ -1041,14 +1039,13 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
                         const int slot = cut0 ? 2 * b : 2 * b + 1;
                         if (fo_ok) {
                             pval[(int64_t)slot * F + n] = RED == 3 ? best : racc;
-                            if constexpr (RED == 3) parg[(int64_t)slot * F + n] = bidx;
+                            if constexpr (RED == 3) parg[(int64_t)slot * F + n] = bidx != MAX_NONE ? bidx : rowptr[re];
                         }
                         if (w == 0 && l == 0) prow[slot] = re;
                     } else if (fo_ok) {
                         if constexpr (RED == 3) {
-                            const bool any = bidx != INT_MAX;
-                            out[(int64_t)re * ldo + n] = any ? best : 0.f;
-                            arg[(int64_t)re * lda + n] = any ? bidx : -1;
+                            out[(int64_t)re * ldo + n] = best;
+                            arg[(int64_t)re * lda + n] = bidx != MAX_NONE ? bidx : rowptr[re];
                         } else {
                             float vv = racc;
                             if constexpr (RED == AGG_MEAN) {
@@ -1060,7 +1057,7 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
                     }
                     racc = 0.f;
                     best = -INFINITY;
-                    bidx = INT_MAX;
+                    bidx = MAX_NONE;
                     first_run = false;
                 }
             }
@@ -1095,7 +1092,7 @@ k_mlp_stream_combine(const float* __restrict__ pval, const int* __restrict__ par
                      int n_slots, int F, const int* __restrict__ rowptr, float* __restrict__ out, int64_t ldo,
                      int* __restrict__ arg, int64_t lda) {
     for (int f = threadIdx.x; f < F; f += 256) {
-        int cur = -1, ba = INT_MAX;
+        int cur = -1, ba = MAX_NONE;
         float bv = 0.f;
         for (int s = 0; s <= n_slots; ++s) {
             const int r = s < n_slots ? prow[s] : -2;
@@ -1103,8 +1100,8 @@ k_mlp_stream_combine(const float* __restrict__ pval, const int* __restrict__ par
             if (r != cur) {
                 if (cur >= 0) {
                     if constexpr (RED == 3) {
-                        out[(int64_t)cur * ldo + f] = ba != INT_MAX ? bv : 0.f;
-                        arg[(int64_t)cur * lda + f] = ba != INT_MAX ? ba : -1;
+                        out[(int64_t)cur * ldo + f] = ba != MAX_NONE ? bv : 0.f;
+                        arg[(int64_t)cur * lda + f] = ba != MAX_NONE ? ba : -1;
                     } else {
                         float v = bv;
                         if constexpr (RED == AGG_MEAN) {
@@ -1121,7 +1118,7 @@ k_mlp_stream_combine(const float* __restrict__ pval, const int* __restrict__ par
             } else {
                 const float v = pval[(int64_t)s * F + f];
                 if constexpr (RED == 3) {
-                    if (v > bv) { bv = v; ba = parg[(int64_t)s * F + f]; }
+                    if (max_beats(v, bv)) { bv = v; ba = parg[(int64_t)s * F + f]; }
                 } else {
                     bv += v;
                 }
@@ -1140,7 +1137,7 @@ __global__ void k_mlp_max_combine(const int4* __restrict__ splits, int F, const 
         int a = parg[(int64_t)sp.y * F + f];
         for (int k = 1; k < sp.z; ++k) {
             const float v = pval[(int64_t)(sp.y + k) * F + f];
-            if (v > b) { b = v; a = parg[(int64_t)(sp.y + k) * F + f]; }
+            if (max_beats(v, b)) { b = v; a = parg[(int64_t)(sp.y + k) * F + f]; }
         }
         Y[(int64_t)sp.x * ldy + f] = b;
         arg[(int64_t)sp.x * lda + f] = a;

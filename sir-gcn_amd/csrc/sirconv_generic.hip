@@ -81,7 +81,7 @@ k_gather_add(const int* __restrict__ col, const int4* __restrict__ items, int64_
 #pragma unroll
                 for (int x = 0; x < VW; ++x) {
                     k[x] = q[j][x] + k[x];                                 // eq[v] + ek[u] (conv.py:45)
-                    if constexpr (ACT == ACT_RELU) k[x] = k[x] > 0.f ? k[x] : 0.f;
+                    if constexpr (ACT == ACT_RELU) k[x] = k[x] <= 0.f ? 0.f : k[x];    // ReLU(NaN) = NaN, as torch.relu
                     else if constexpr (ACT == ACT_LEAKY) k[x] = k[x] > 0.f ? k[x] : k[x] * slope;
                 }
                 if constexpr (SM) {
@@ -228,7 +228,7 @@ k_seg_max(const int4* __restrict__ items, int64_t n_items, int F, const float* _
                 ld<VW>(v, M + (int64_t)e * ldm + c * VW);
 #pragma unroll
                 for (int x = 0; x < VW; ++x)
-                    if (barg[j][x] < 0 || v[x] > best[j][x]) { best[j][x] = v[x]; barg[j][x] = e; }
+                    if (barg[j][x] < 0 || max_beats(v[x], best[j][x])) { best[j][x] = v[x]; barg[j][x] = e; }
             }
         }
     }
@@ -258,7 +258,7 @@ k_seg_max_combine(const int4* __restrict__ splits, int64_t n_splits, int F, cons
         int a = parg[(int64_t)sp.y * F + f];
         for (int k = 1; k < sp.z; ++k) {
             const float v = pval[(int64_t)(sp.y + k) * F + f];
-            if (v > b) { b = v; a = parg[(int64_t)(sp.y + k) * F + f]; }
+            if (max_beats(v, b)) { b = v; a = parg[(int64_t)(sp.y + k) * F + f]; }
         }
         Y[(int64_t)sp.x * ldy + f] = b;
         arg[(int64_t)sp.x * lda + f] = a;

@@ -96,7 +96,7 @@ __device__ __forceinline__ void walk_rows2(int64_t r0, int64_t r1, const float* 
 // ops of torch's relu / leaky_relu and their backward (x > 0 ? g : 0 / g * slope)
 template <int ACT>
 __device__ __forceinline__ float gn_act(float y, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y > 0.f ? y : 0.f;
+    if constexpr (ACT == SIR_ACT_RELU) return y <= 0.f ? 0.f : y;         // ReLU(NaN) = NaN, as torch.relu
     else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? y : y * slope;
     else return y;
 }

@@ -12,6 +12,24 @@ enum { ACT_IDENTITY = 0, ACT_RELU = 1, ACT_LEAKY = 2, ACT_GELU = 3, ACT_GELU_TAN
 enum { MODE_FWD = 0, MODE_BWD_DST = 1, MODE_BWD_SRC = 2 };
 enum { ST_F32 = 0, ST_BF16 = 1, ST_F16 = 2 };     // feature storage dtype (SIR_DTYPE_*)
 
+// The order of every maximum of the library and of every combine of its partials (include/sirconv.h,
+// "Non-finite values"): torch.max's — a NaN beats every number — and the FIRST of equal candidates, or of
+// NaNs, stays.  Candidates and partials are visited in edge order, so "v replaces best" is strict: v > best,
+// or v is the first NaN.  The result is that of the one-lane walk whatever the plan cuts a row into.
+__device__ __forceinline__ bool max_beats(float v, float best) { return !(v <= best) && best == best; }
+// The fused walks seed (best, index) = (-inf, MAX_NONE) and test max_beats alone, so an index still MAX_NONE
+// after a walk that saw edges means "every candidate was -inf": the value -inf stands and the arg is the first
+// edge — a row with edges always takes an edge; only a row without edges gives 0 / -1.
+constexpr int MAX_NONE = 0x7fffffff;
+__device__ __forceinline__ int max_arg(int bidx, int e0, int e1) {
+    return bidx != MAX_NONE ? bidx : (e1 > e0 ? e0 : -1);
+}
+// merging two partials over interleaved edges (the half-waves of an MFMA tile): the earlier edge wins among equals
+__device__ __forceinline__ bool max_merges(float v, int vi, float best, int bidx) {
+    const bool same = v == best || (v != v && best != best);
+    return max_beats(v, best) || (same && vi < bidx);
+}
+
 // Feature pointers carry the storage dtype of the call (ST_*); norms and partial rows are fp32.
 struct EdgeArgs {
     const int* rowptr;

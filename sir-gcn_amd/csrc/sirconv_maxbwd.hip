@@ -347,7 +347,9 @@ k_maxb_dw(const int* __restrict__ rowptr, const int* __restrict__ col, const int
 #pragma unroll
         for (int h = 0; h < SIR_MAXB_DW_ROWS; ++h) {
             const int rr = two ? r + h : r;
-            const float4 q4 = cok ? ld4(Q + (int64_t)rr * ldq + cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+            // Q[v] of a row without edges is don't-care storage (it may hold NaN, and 0 * NaN is NaN): not read
+            const bool has = rowptr[rr + 1] > rowptr[rr];
+            const float4 q4 = (cok && has) ? ld4(Q + (int64_t)rr * ldq + cq) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float yi = __shfl(y[h], 8 * i + i8);

@@ -59,7 +59,7 @@ __device__ __forceinline__ void nst(float* __restrict__ p, const float (&s)[VW])
 // torch's relu / leaky_relu and their backward (gn_act / gn_act_bwd of sirconv_graphnorm.hip)
 template <int ACT>
 __device__ __forceinline__ float nn_act(float y, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y > 0.f ? y : 0.f;
+    if constexpr (ACT == SIR_ACT_RELU) return y <= 0.f ? 0.f : y;         // ReLU(NaN) = NaN, as torch.relu
     else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? y : y * slope;
     else return y;
 }

@@ -155,10 +155,17 @@ k_pool_fwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_c
 #pragma unroll
     for (int x = 0; x < VW; ++x) { acc[x] = 0.f; am[x] = -1; }
     if constexpr (OP == SIR_POOL_MAX) {
-        pool_walk<T, VW>(s.r0, s.r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
+        // the slab's first row seeds (value, arg) whatever it holds — no "nothing seen yet" test in the walk —
+        // and a later row replaces it in the maximum's order (max_beats: strict, so the first wins)
+        if (s.r0 < s.r1) {
+            pld<T, VW>(acc, X + s.r0 * ldx + c * VW);
+#pragma unroll
+            for (int x = 0; x < VW; ++x) am[x] = (int)(s.r0 - s.g0);
+        }
+        pool_walk<T, VW>(s.r0 + 1, s.r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
 #pragma unroll
             for (int x = 0; x < VW; ++x)
-                if (am[x] < 0 || v[x] > acc[x]) { acc[x] = v[x]; am[x] = (int)(i - s.g0); }   // strict >: first wins
+                if (max_beats(v[x], acc[x])) { acc[x] = v[x]; am[x] = (int)(i - s.g0); }
         });
     } else {
         pool_walk<T, VW>(s.r0, s.r1, X, ldx, c, [&](int64_t, const float (&v)[VW]) {
@@ -210,7 +217,7 @@ k_pool_combine(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int
         for (int64_t j = 1; j < nslab; ++j) {
             const float v = work[(t0 + j) * F + c];
             if constexpr (OP == SIR_POOL_MAX) {
-                if (v > acc) { acc = v; am = warg[(t0 + j) * F + c]; }
+                if (max_beats(v, acc)) { acc = v; am = warg[(t0 + j) * F + c]; }
             } else {
                 acc += v;
             }

@@ -41,7 +41,7 @@ struct Elt<SIR_DTYPE_F16> {
 
 template <int ACT>
 __device__ __forceinline__ float act_f(float x, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return x > 0.f ? x : 0.f;
+    if constexpr (ACT == SIR_ACT_RELU) return x <= 0.f ? 0.f : x;         // ReLU(NaN) = NaN, as torch.relu
     else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return x > 0.f ? x : x * slope;
     else return x;
 }

@@ -34,38 +34,12 @@
 #include "sirconv_internal.h"
 #include "sirconv_gemm_util.h"
 #include "sirconv_dropout.h"
+#include "sirconv_gemm_nt.h"
 
 namespace sir {
 namespace {
 using namespace gemm;
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-
-constexpr int KC = 32;          // contraction elements per LDS stage (two k16 MFMA steps)
-
-#ifndef SIR_HR
-#define SIR_HR 8                // headroom bits of a reset running scale (see next_se)
-#endif
-
-// Smallest e with |m| < 2^e for normal m (e = -126 for 0 and subnormals, 129 for inf/nan).
-__device__ inline int bexp(float m) { return (int)((__float_as_uint(m) >> 23) & 255u) - 126; }
-// scale exponent for a running binade e: |x| * 2^(15 - e) < 2^15, clamped to a normal float
-__device__ inline int scale_exp(int e) { int s = 15 - e; return s > 126 ? 126 : s; }
-// Running scale of a data row / column with hysteresis: a chunk whose binade e_c still fits
-// (|x| * 2^se < 2^15) keeps the current scale; otherwise the scale is reset with SIR_HR bits of
-// headroom, so a row's scale changes (and its accumulators are rescaled) only when a chunk
-// exceeds the row's earlier maximum by more than 2^SIR_HR — once per row in practice, at its
-// first chunk.  Scaled values stay in [2^-14, 2^15) over >= 20 binades below the maximum, where
-// the fp16 hi/lo pair is exact to ~22 bits; the split is scale-invariant there, so the result
-// does not depend on which power-of-two scale was in force.
-constexpr int SE_INIT = 127;    // no chunk seen yet
-__device__ inline int next_se(int se_old, int e_c) {
-    if (e_c + se_old <= 15) return se_old;
-    const int s = 15 - SIR_HR - e_c;
-    return s > 126 ? 126 : s;
-}
 // compensated (Kahan) accumulation: s += x with the rounding error carried in c (no fp contraction
 // in this file, so the compensation is not optimised away)
 __device__ inline void kahan_add(float& s, float& c, float x) {
@@ -73,16 +47,6 @@ __device__ inline void kahan_add(float& s, float& c, float x) {
     const float t = s + y;
     c = (t - s) - y;
     s = t;
-}
-__device__ inline float pow2(int e) { e = e < -126 ? -126 : (e > 127 ? 127 : e); return __uint_as_float((uint32_t)(e + 127) << 23); }
-// feature dropout of QK (sirconv_dropout.h) on 4 consecutive output columns n .. n+3 of one row
-__device__ inline void drop4(const Drop& d, int64_t row, int n, float4& o) {
-    const uint32_t rh = drop_row_hash(d, row);
-    const int c = d.col0 + n;
-    o.x = drop_keep(d, rh, c + 0) ? o.x * d.scale : 0.f;
-    o.y = drop_keep(d, rh, c + 1) ? o.y * d.scale : 0.f;
-    o.z = drop_keep(d, rh, c + 2) ? o.z * d.scale : 0.f;
-    o.w = drop_keep(d, rh, c + 3) ? o.w * d.scale : 0.f;
 }
 
 // sigma'(z) * x from the sign of the gate (z or sigma(z): the same sign for the ReLU family)
@@ -108,29 +72,6 @@ k_gate_dact(float* __restrict__ C, int64_t ldc, const float* __restrict__ gate, 
     C[r * ldc + c] = gate_dact(gate[r * ldc + c], C[r * ldc + c], relu, slope);
 }
 
-// hi/lo fp16 split of 8 floats scaled by s (exact power of two)
-// hi = fp16(x s), lo = fp16(x s - hi), one v_fma_mix each, written into the halves of the fragment
-// registers (x s is exact, and x s - hi is exact in the fused op: the same bits as rounding y = x s
-// and y - hi separately, sirconv_gemm_w.hip).  s_nop 1: the VALU-write -> MFMA-read wait states
-// (the hazard recognizer does not look inside inline asm).
-__device__ inline void split8_mix(float4 a, float4 b, float s, h8& hi, h8& lo) {
-    uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
-    asm volatile(
-        "v_fma_mixlo_f16 %0, %8, %16, 0\n\tv_fma_mixhi_f16 %0, %9, %16, 0\n\t"
-        "v_fma_mixlo_f16 %1, %10, %16, 0\n\tv_fma_mixhi_f16 %1, %11, %16, 0\n\t"
-        "v_fma_mixlo_f16 %2, %12, %16, 0\n\tv_fma_mixhi_f16 %2, %13, %16, 0\n\t"
-        "v_fma_mixlo_f16 %3, %14, %16, 0\n\tv_fma_mixhi_f16 %3, %15, %16, 0\n\t"
-        "v_fma_mixlo_f16 %4, %8, %16, -%0 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %4, %9, %16, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %5, %10, %16, -%1 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %5, %11, %16, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %6, %12, %16, -%2 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %6, %13, %16, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %7, %14, %16, -%3 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %7, %15, %16, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-        : "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(s));
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    hi = __builtin_bit_cast(h8, u4{h0, h1, h2, h3});
-    lo = __builtin_bit_cast(h8, u4{l0, l1, l2, l3});
-}
 // the same split in plain C (~4.5 VALU per element), for k_gemm_nt (the asm form costs it a spill in
 // the loop) and the small kernels
 #define SIR_SPLIT1(x, i) { const float y_ = (x) * s; const _Float16 h_ = (_Float16)y_; hi[i] = h_; lo[i] = (_Float16)(y_ - (float)h_); }
@@ -140,12 +81,6 @@ __device__ inline void split8(float4 a, float4 b, float s, h8& hi, h8& lo) {
 }
 #undef SIR_SPLIT1
 
-// m = max(m, |v|) in two v_max3_f32 with |.| source modifiers (fmaxf makes hipcc canonicalise every
-// input first)
-__device__ inline float fmax4_mix(float m, float4 v) {
-    asm("v_max3_f32 %0, %0, |%1|, |%2|\n\tv_max3_f32 %0, %0, |%3|, |%4|" : "+v"(m) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-    return m;
-}
 __device__ inline float fmax4(float m, float4 v) {
     return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
 }
@@ -445,7 +380,6 @@ k_gemm_nt(const float* __restrict__ A, int64_t lda, int64_t M, int K,
 // are those of k_gemm_nt<2, 4, 4, 2, true>: results are bit-identical.
 // The hi / lo split is split8_mix and the chunk's row maximum fmax4_mix (2 VGPRs spilled outside the
 // chunk loop), bit-identical to the plain C forms.
-constexpr int NT_P_NMAX = 512;
 
 // GATE: C = sigma'(gate) * (A B^T) (gate [M, N] with C's leading dimension; ReLU: gate > 0 ? x : 0,
 // LeakyReLU: gate > 0 ? x : x * slope — torch's threshold / leaky_relu backward with the activation's
@@ -1659,6 +1593,16 @@ static int lt_env(const char* name, int dflt) {
     const char* e = getenv(name);
     return (e != nullptr && e[0] != 0) ? atoi(e) : dflt;
 }
+// The plain persistent NT GEMM as two 4-wave blocks per CU (k_gemm_nt_p2, sirconv_gemm_nt2.hip) or as
+// one 8-wave block (k_gemm_nt_p): env SIR_NT_2B = 1 / 0 per call, unset: by shape (nt_2b_auto).
+#ifndef SIR_NT_2B
+#define SIR_NT_2B -1            // -1: by shape
+#endif
+// The layer's shapes at H = 256, each measured faster on the two-block kernel (profiles/r07_ab_gemm_nt_2b.txt);
+// every other shape stays on k_gemm_nt_p until it is measured.
+static bool nt_2b_auto(int K, int N) {
+    return (K == 256 && (N == 256 || N == 512)) || (K == 512 && N == 256);
+}
 #ifndef SIR_LT_BLOCKS
 #define SIR_LT_BLOCKS 512       // k_gemm_lt TN: row splits until about this many blocks
 #endif
@@ -1847,7 +1791,13 @@ hipError_t run_gemm_nt(const float* A, int64_t lda, int64_t M, int K, const void
     const float* inv = reinterpret_cast<const float*>(static_cast<const char*>(packed) + (int64_t)kc * 4 * np * 32);
     const bool kfull = K % KC == 0;
     if (M < gemm_small_rows()) return run_gemm_nt_s(A, lda, M, K, packed, N, bias, C, ldc, st, drop);
-    if (N > 128 && np <= NT_P_NMAX && kfull && (kc == 4 || kc == 8 || kc == 16) &&
+    const bool persistent = N > 128 && np <= NT_P_NMAX && kfull && (kc == 4 || kc == 8 || kc == 16);
+    // env SIR_NT_2B: 1 = the two-block kernel (k_gemm_nt_p2), 0 = k_gemm_nt_p, unset = by shape
+    const int two = lt_env("SIR_NT_2B", SIR_NT_2B);
+    if (persistent && (two < 0 ? nt_2b_auto(K, N) : two != 0) &&
+        launch_gemm_nt_p2(A, lda, M, kc, packed, N, bias, C, ldc, st, drop))
+        return hipGetLastError();
+    if (persistent &&
         launch_gemm_nt_p<0>(A, lda, M, kc, packed, N, bias, C, ldc, st, drop, nullptr, 0, 0.f))
         return hipGetLastError();
     if (N > 128) {

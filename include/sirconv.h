@@ -23,7 +23,8 @@
  *    residual fused: sir_graph_norm_act_fwd / _bwd;
  *  - BatchNorm1d / LayerNorm on node features (models/norm.py:53-60, built by GetNorm, norm.py:68-82) with
  *    the stack's activation and residual fused: sir_batch_norm_stats / sir_batch_norm_act_fwd / _bwd and
- *    sir_layer_norm_act_fwd / _bwd;
+ *    sir_layer_norm_act_fwd / _bwd; the layer's nn.Dropout between activation and residual fused
+ *    into all three: sir_{batch,layer,graph}_norm_act_drop_fwd / _bwd;
  *  - the graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling, dgl.broadcast_nodes; ogbg-molhiv/model.py:69,85,
  *    zinc/model.py:41): sir_graph_pool_fwd / _bwd (sir_graph_pool_work_floats, sir_graph_pool_slab_rows);
  *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm.
@@ -60,7 +61,9 @@
  *    NaN, as arg; a row with edges always returns one of its edges (all -Inf: -Inf and the first edge),
  *    only a row without edges returns 0 / -1.  The rule does not depend on the plan's chunk, the
  *    route, or the readout's slab cut.
- *    Deviations from torch: (1) a dropped element of the feature dropout is 0 whatever it held
+ *    Deviations from torch: (1) a dropped element of the feature dropout, and of the layer dropout of
+ *    sir_batch_norm_act_drop_* / sir_layer_norm_act_drop_* / sir_graph_norm_act_drop_* (forward: +0 before
+ *    the add of R, which propagates; backward: g0 = 0), is 0 whatever it held
  *    (nn.Dropout gives NaN * 0 = NaN); a kept one propagates.  (2) sigma'(z) of the ReLU family at a
  *    NaN z is the "z > 0 is false" branch (0 for ReLU, slope for LeakyReLU), where torch's
  *    threshold_backward passes the gradient; rows such an edge does not touch are unaffected.  (3) The
@@ -575,6 +578,52 @@ int sir_layer_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t
                            const float* weight, const float* bias, const float* mean, const float* rstd, int act,
                            float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Layer dropout fused into the three norm passes — the nn.Dropout the node-level models put between the
+ * layer's activation and its residual add (ogbn-arxiv/model.py:49,70: norm -> act -> dropout -> + resid;
+ * zinc/model.py:24,56: norm -> act -> dropout).  Each entry has the argument list of its *_act_* sibling
+ * with a trailing `drop` before `stream`.  Added under ABI 17 (new symbols only).
+ *   forward : out = d + R,  d = keep(row, col) ? act(y) * scale : +0
+ *   backward: g = act'(y) g0,  g0 = keep(row, col) ? dY * scale : 0 (one fp32 rounding); g then stands
+ *             wherever the sibling takes act'(y) dY: both BatchNorm backward launches, the LayerNorm row
+ *             backward and its dw / db partials, the GraphNorm backward and its three partial arrays.
+ *             R's gradient stays dY itself (the caller's).
+ * keep, scale and the seed are sir_dropout_t's: element (row, col) of the [M, N] (GraphNorm: [V, F],
+ * row = the row of X, not the row within its graph) output draws the bits sir_dropout_apply writes for
+ * that block at col0 = 0; no mask is stored, the backward recomputes it.  The op order is torch's
+ * autograd order for act -> dropout -> add, so the result is bit-identical to the sibling's output
+ * (R = NULL) times the mask, plus R.  drop == NULL or p <= 0: the sibling's kernels, bit for bit;
+ * p >= 1: out = R (or +0), dX = 0; a NaN p: SIR_EINVAL; seed_ptr as in sir_dropout_t (a captured step
+ * draws a fresh mask on every replay, and the backward given the same pointer reads the same word).
+ * Give the layer a seed word no conv of the step uses: the conv's Q dropout hashes the same (row, col).
+ * Partitions, vector widths and determinism are the siblings'.
+ * ------------------------------------------------------------------------------------------- */
+int sir_batch_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const double* mean,
+                                const double* invstd, const float* weight, const float* bias, int act, float slope,
+                                const float* R, int64_t ldr, float* Y, int64_t ldy, const sir_dropout_t* drop,
+                                void* stream);
+int sir_batch_norm_act_drop_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                                const double* mean, const double* invstd, const float* weight, const float* bias,
+                                int act, float slope, int training, float* dX, int64_t lddx, float* dweight,
+                                float* dbias, float* work, const sir_dropout_t* drop, void* stream);
+int sir_layer_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight,
+                                const float* bias, float eps, int act, float slope, const float* R, int64_t ldr,
+                                float* Y, int64_t ldy, float* mean, float* rstd, const sir_dropout_t* drop,
+                                void* stream);
+int sir_layer_norm_act_drop_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                                const float* weight, const float* bias, const float* mean, const float* rstd, int act,
+                                float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
+                                const sir_dropout_t* drop, void* stream);
+int sir_graph_norm_act_drop_fwd(const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
+                                const float* weight, const float* bias, const float* mean_scale, float eps, int act,
+                                float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean,
+                                float* std_, const sir_dropout_t* drop, void* stream);
+int sir_graph_norm_act_drop_bwd(const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
+                                const float* dY, int64_t ldg, const float* weight, const float* bias,
+                                const float* mean_scale, const float* mean, const float* std_, int act, float slope,
+                                float* dX, int64_t lddx, float* dw_part, float* dms_part, float* db_part,
+                                const sir_dropout_t* drop, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling: ogbg-molhiv/model.py:69,85, zinc/model.py:41,

@@ -12,6 +12,7 @@
 #include "sirconv.h"
 #include "sirconv_internal.h"
 #include "sirconv_eedge.h"
+#include "sirconv_normdrop.h"
 
 namespace {
 
@@ -60,6 +61,121 @@ int finish(const char* fn, hipError_t err, const char* why) {
     if (err == hipErrorInvalidValue)
         return fail(SIR_EUNSUPPORTED, fn, "sign-mask mode needs 16-B aligned full-wave rows");
     return fail(SIR_ELAUNCH, fn, hipGetErrorString(err));
+}
+
+// the layer dropout of the fused norm entries: a NaN p is an error (p <= 0: none, p >= 1: everything)
+int check_layer_drop(const char* fn, const sir_dropout_t* d) {
+    if (d != nullptr && d->p != d->p) return fail(SIR_EINVAL, fn, "dropout p is NaN");
+    return SIR_OK;
+}
+
+// the bodies of the fused norm entries and of their *_drop_* siblings (drop = NULL: the entries without dropout)
+int graph_norm_act_fwd(const char* fn, const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
+                       const float* weight, const float* bias, const float* mean_scale, float eps, int act, float slope,
+                       const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* std_,
+                       const sir_dropout_t* drop, void* stream) {
+    if (B < 0 || F <= 0 || F > 65536) return fail(SIR_EINVAL, fn, "bad shape");
+    if (ldx < F || ldy < F || (R != nullptr && ldr < F)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= F");
+    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
+        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
+    if (check_layer_drop(fn, drop) != SIR_OK) return SIR_EINVAL;
+    if (B > 0 && (off == nullptr || X == nullptr || weight == nullptr || Y == nullptr || mean == nullptr ||
+                  std_ == nullptr))
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_graph_norm_drop_fwd(off, B, (int)F, X, ldx, weight, bias, mean_scale, eps, act, slope, R,
+                                                   ldr, Y, ldy, mean, std_, to_drop(drop, 0),
+                                                   static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int graph_norm_act_bwd(const char* fn, const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
+                       const float* dY, int64_t ldg, const float* weight, const float* bias, const float* mean_scale,
+                       const float* mean, const float* std_, int act, float slope, float* dX, int64_t lddx,
+                       float* dw_part, float* dms_part, float* db_part, const sir_dropout_t* drop, void* stream) {
+    if (B < 0 || F <= 0 || F > 65536) return fail(SIR_EINVAL, fn, "bad shape");
+    if (ldx < F || ldg < F || lddx < F) return fail(SIR_EINVAL, fn, "leading dimensions must be >= F");
+    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
+        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
+    if (check_layer_drop(fn, drop) != SIR_OK) return SIR_EINVAL;
+    if (B > 0 && (off == nullptr || X == nullptr || dY == nullptr || weight == nullptr || mean == nullptr ||
+                  std_ == nullptr || dX == nullptr || dw_part == nullptr || db_part == nullptr))
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    if (mean_scale != nullptr && dms_part == nullptr && B > 0) return fail(SIR_EINVAL, fn, "dms_part needed");
+    return finish(fn, sir::run_graph_norm_drop_bwd(off, B, (int)F, X, ldx, dY, ldg, weight, bias, mean_scale, mean, std_,
+                                                   act, slope, dX, lddx, dw_part, dms_part, db_part, to_drop(drop, 0),
+                                                   static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int check_nodenorm(const char* fn, int64_t M, int64_t N, int64_t n_max, int act) {
+    if (M < 0 || M > ((int64_t)1 << 37)) return fail(SIR_EINVAL, fn, "M out of range");
+    if (N <= 0 || N > n_max) return fail(SIR_EINVAL, fn, n_max == 1024 ? "N must be in [1, 1024]" : "N must be in [1, 65536]");
+    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
+        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
+    return SIR_OK;
+}
+
+int batch_norm_act_fwd(const char* fn, const float* X, int64_t ldx, int64_t M, int64_t N, const double* mean,
+                       const double* invstd, const float* weight, const float* bias, int act, float slope,
+                       const float* R, int64_t ldr, float* Y, int64_t ldy, const sir_dropout_t* drop, void* stream) {
+    int rc = check_nodenorm(fn, M, N, 65536, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldy < N || (R != nullptr && ldr < N)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (check_layer_drop(fn, drop) != SIR_OK) return SIR_EINVAL;
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr || Y == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_batch_norm_act_drop_fwd(X, ldx, M, (int)N, mean, invstd, weight, bias, act, slope, R, ldr,
+                                                       Y, ldy, to_drop(drop, 0), static_cast<hipStream_t>(stream)),
+                  nullptr);
+}
+
+int batch_norm_act_bwd(const char* fn, const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                       const double* mean, const double* invstd, const float* weight, const float* bias, int act,
+                       float slope, int training, float* dX, int64_t lddx, float* dweight, float* dbias, float* work,
+                       const sir_dropout_t* drop, void* stream) {
+    int rc = check_nodenorm(fn, M, N, 65536, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldg < N || lddx < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (check_layer_drop(fn, drop) != SIR_OK) return SIR_EINVAL;
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || dY == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr ||
+        dX == nullptr || dweight == nullptr || dbias == nullptr || work == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    if ((reinterpret_cast<uintptr_t>(work) & 7u) != 0) return fail(SIR_EINVAL, fn, "work must be 8-B aligned");
+    return finish(fn, sir::run_batch_norm_act_drop_bwd(X, ldx, dY, ldg, M, (int)N, mean, invstd, weight, bias, act, slope,
+                                                       training, dX, lddx, dweight, dbias, work, to_drop(drop, 0),
+                                                       static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int layer_norm_act_fwd(const char* fn, const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight,
+                       const float* bias, float eps, int act, float slope, const float* R, int64_t ldr, float* Y,
+                       int64_t ldy, float* mean, float* rstd, const sir_dropout_t* drop, void* stream) {
+    int rc = check_nodenorm(fn, M, N, 1024, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldy < N || (R != nullptr && ldr < N)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (check_layer_drop(fn, drop) != SIR_OK) return SIR_EINVAL;
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || weight == nullptr || bias == nullptr || Y == nullptr || mean == nullptr || rstd == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_layer_norm_act_drop_fwd(X, ldx, M, (int)N, weight, bias, eps, act, slope, R, ldr, Y, ldy,
+                                                       mean, rstd, to_drop(drop, 0), static_cast<hipStream_t>(stream)),
+                  nullptr);
+}
+
+int layer_norm_act_bwd(const char* fn, const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                       const float* weight, const float* bias, const float* mean, const float* rstd, int act,
+                       float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
+                       const sir_dropout_t* drop, void* stream) {
+    int rc = check_nodenorm(fn, M, N, 1024, act);
+    if (rc != SIR_OK) return rc;
+    if (ldx < N || ldg < N || lddx < N || ldp < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
+    if (check_layer_drop(fn, drop) != SIR_OK) return SIR_EINVAL;
+    if (M == 0) return SIR_OK;
+    if (X == nullptr || dY == nullptr || weight == nullptr || bias == nullptr || mean == nullptr || rstd == nullptr ||
+        dX == nullptr || dw_part == nullptr || db_part == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL buffer");
+    return finish(fn, sir::run_layer_norm_act_drop_bwd(X, ldx, dY, ldg, M, (int)N, weight, bias, mean, rstd, act, slope,
+                                                       dX, lddx, dw_part, db_part, ldp, to_drop(drop, 0),
+                                                       static_cast<hipStream_t>(stream)), nullptr);
 }
 
 }  // namespace
@@ -841,16 +957,16 @@ int sir_graph_norm_act_fwd(const int64_t* off, int64_t B, int64_t F, const float
                            const float* weight, const float* bias, const float* mean_scale, float eps, int act,
                            float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* std_,
                            void* stream) {
-    const char* fn = "sir_graph_norm_act_fwd";
-    if (B < 0 || F <= 0 || F > 65536) return fail(SIR_EINVAL, fn, "bad shape");
-    if (ldx < F || ldy < F || (R != nullptr && ldr < F)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= F");
-    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
-        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
-    if (B > 0 && (off == nullptr || X == nullptr || weight == nullptr || Y == nullptr || mean == nullptr ||
-                  std_ == nullptr))
-        return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_graph_norm_fwd(off, B, (int)F, X, ldx, weight, bias, mean_scale, eps, act, slope, R, ldr,
-                                              Y, ldy, mean, std_, static_cast<hipStream_t>(stream)), nullptr);
+    return graph_norm_act_fwd("sir_graph_norm_act_fwd", off, B, F, X, ldx, weight, bias, mean_scale, eps, act, slope, R,
+                              ldr, Y, ldy, mean, std_, nullptr, stream);
+}
+
+int sir_graph_norm_act_drop_fwd(const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
+                                const float* weight, const float* bias, const float* mean_scale, float eps, int act,
+                                float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean,
+                                float* std_, const sir_dropout_t* drop, void* stream) {
+    return graph_norm_act_fwd("sir_graph_norm_act_drop_fwd", off, B, F, X, ldx, weight, bias, mean_scale, eps, act, slope,
+                              R, ldr, Y, ldy, mean, std_, drop, stream);
 }
 
 int sir_graph_norm_bwd(const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
@@ -873,29 +989,20 @@ int sir_graph_norm_act_bwd(const int64_t* off, int64_t B, int64_t F, const float
                            const float* dY, int64_t ldg, const float* weight, const float* bias,
                            const float* mean_scale, const float* mean, const float* std_, int act, float slope,
                            float* dX, int64_t lddx, float* dw_part, float* dms_part, float* db_part, void* stream) {
-    const char* fn = "sir_graph_norm_act_bwd";
-    if (B < 0 || F <= 0 || F > 65536) return fail(SIR_EINVAL, fn, "bad shape");
-    if (ldx < F || ldg < F || lddx < F) return fail(SIR_EINVAL, fn, "leading dimensions must be >= F");
-    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
-        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
-    if (B > 0 && (off == nullptr || X == nullptr || dY == nullptr || weight == nullptr || mean == nullptr ||
-                  std_ == nullptr || dX == nullptr || dw_part == nullptr || db_part == nullptr))
-        return fail(SIR_EINVAL, fn, "NULL buffer");
-    if (mean_scale != nullptr && dms_part == nullptr && B > 0) return fail(SIR_EINVAL, fn, "dms_part needed");
-    return finish(fn, sir::run_graph_norm_bwd(off, B, (int)F, X, ldx, dY, ldg, weight, bias, mean_scale, mean, std_,
-                                              act, slope, dX, lddx, dw_part, dms_part, db_part,
-                                              static_cast<hipStream_t>(stream)), nullptr);
+    return graph_norm_act_bwd("sir_graph_norm_act_bwd", off, B, F, X, ldx, dY, ldg, weight, bias, mean_scale, mean, std_,
+                              act, slope, dX, lddx, dw_part, dms_part, db_part, nullptr, stream);
+}
+
+int sir_graph_norm_act_drop_bwd(const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
+                                const float* dY, int64_t ldg, const float* weight, const float* bias,
+                                const float* mean_scale, const float* mean, const float* std_, int act, float slope,
+                                float* dX, int64_t lddx, float* dw_part, float* dms_part, float* db_part,
+                                const sir_dropout_t* drop, void* stream) {
+    return graph_norm_act_bwd("sir_graph_norm_act_drop_bwd", off, B, F, X, ldx, dY, ldg, weight, bias, mean_scale, mean,
+                              std_, act, slope, dX, lddx, dw_part, dms_part, db_part, drop, stream);
 }
 
 // ------------------------------------------------------------------------------ BatchNorm / LayerNorm
-static int check_nodenorm(const char* fn, int64_t M, int64_t N, int64_t n_max, int act) {
-    if (M < 0 || M > ((int64_t)1 << 37)) return fail(SIR_EINVAL, fn, "M out of range");
-    if (N <= 0 || N > n_max) return fail(SIR_EINVAL, fn, n_max == 1024 ? "N must be in [1, 1024]" : "N must be in [1, 65536]");
-    if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
-        return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
-    return SIR_OK;
-}
-
 int64_t sir_batch_norm_work_floats(int64_t M, int64_t N) {
     if (M < 0 || M > ((int64_t)1 << 37) || N <= 0 || N > 65536) return -1;
     return sir::batch_norm_work_floats(M, N);
@@ -921,33 +1028,32 @@ int sir_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int64_t N, floa
 int sir_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const double* mean, const double* invstd,
                            const float* weight, const float* bias, int act, float slope, const float* R, int64_t ldr,
                            float* Y, int64_t ldy, void* stream) {
-    const char* fn = "sir_batch_norm_act_fwd";
-    int rc = check_nodenorm(fn, M, N, 65536, act);
-    if (rc != SIR_OK) return rc;
-    if (ldx < N || ldy < N || (R != nullptr && ldr < N)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
-    if (M == 0) return SIR_OK;
-    if (X == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr || Y == nullptr)
-        return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_batch_norm_act_fwd(X, ldx, M, (int)N, mean, invstd, weight, bias, act, slope, R, ldr, Y,
-                                                  ldy, static_cast<hipStream_t>(stream)), nullptr);
+    return batch_norm_act_fwd("sir_batch_norm_act_fwd", X, ldx, M, N, mean, invstd, weight, bias, act, slope, R, ldr, Y,
+                              ldy, nullptr, stream);
+}
+
+int sir_batch_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const double* mean,
+                                const double* invstd, const float* weight, const float* bias, int act, float slope,
+                                const float* R, int64_t ldr, float* Y, int64_t ldy, const sir_dropout_t* drop,
+                                void* stream) {
+    return batch_norm_act_fwd("sir_batch_norm_act_drop_fwd", X, ldx, M, N, mean, invstd, weight, bias, act, slope, R, ldr,
+                              Y, ldy, drop, stream);
 }
 
 int sir_batch_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
                            const double* mean, const double* invstd, const float* weight, const float* bias, int act,
                            float slope, int training, float* dX, int64_t lddx, float* dweight, float* dbias,
                            float* work, void* stream) {
-    const char* fn = "sir_batch_norm_act_bwd";
-    int rc = check_nodenorm(fn, M, N, 65536, act);
-    if (rc != SIR_OK) return rc;
-    if (ldx < N || ldg < N || lddx < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
-    if (M == 0) return SIR_OK;
-    if (X == nullptr || dY == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr ||
-        dX == nullptr || dweight == nullptr || dbias == nullptr || work == nullptr)
-        return fail(SIR_EINVAL, fn, "NULL buffer");
-    if ((reinterpret_cast<uintptr_t>(work) & 7u) != 0) return fail(SIR_EINVAL, fn, "work must be 8-B aligned");
-    return finish(fn, sir::run_batch_norm_act_bwd(X, ldx, dY, ldg, M, (int)N, mean, invstd, weight, bias, act, slope,
-                                                  training, dX, lddx, dweight, dbias, work,
-                                                  static_cast<hipStream_t>(stream)), nullptr);
+    return batch_norm_act_bwd("sir_batch_norm_act_bwd", X, ldx, dY, ldg, M, N, mean, invstd, weight, bias, act, slope,
+                              training, dX, lddx, dweight, dbias, work, nullptr, stream);
+}
+
+int sir_batch_norm_act_drop_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                                const double* mean, const double* invstd, const float* weight, const float* bias,
+                                int act, float slope, int training, float* dX, int64_t lddx, float* dweight,
+                                float* dbias, float* work, const sir_dropout_t* drop, void* stream) {
+    return batch_norm_act_bwd("sir_batch_norm_act_drop_bwd", X, ldx, dY, ldg, M, N, mean, invstd, weight, bias, act,
+                              slope, training, dX, lddx, dweight, dbias, work, drop, stream);
 }
 
 int64_t sir_layer_norm_bwd_parts(int64_t M, int64_t N) {
@@ -958,32 +1064,32 @@ int64_t sir_layer_norm_bwd_parts(int64_t M, int64_t N) {
 int sir_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight, const float* bias,
                            float eps, int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
                            float* mean, float* rstd, void* stream) {
-    const char* fn = "sir_layer_norm_act_fwd";
-    int rc = check_nodenorm(fn, M, N, 1024, act);
-    if (rc != SIR_OK) return rc;
-    if (ldx < N || ldy < N || (R != nullptr && ldr < N)) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
-    if (M == 0) return SIR_OK;
-    if (X == nullptr || weight == nullptr || bias == nullptr || Y == nullptr || mean == nullptr || rstd == nullptr)
-        return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_layer_norm_act_fwd(X, ldx, M, (int)N, weight, bias, eps, act, slope, R, ldr, Y, ldy, mean,
-                                                  rstd, static_cast<hipStream_t>(stream)), nullptr);
+    return layer_norm_act_fwd("sir_layer_norm_act_fwd", X, ldx, M, N, weight, bias, eps, act, slope, R, ldr, Y, ldy, mean,
+                              rstd, nullptr, stream);
+}
+
+int sir_layer_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight,
+                                const float* bias, float eps, int act, float slope, const float* R, int64_t ldr,
+                                float* Y, int64_t ldy, float* mean, float* rstd, const sir_dropout_t* drop,
+                                void* stream) {
+    return layer_norm_act_fwd("sir_layer_norm_act_drop_fwd", X, ldx, M, N, weight, bias, eps, act, slope, R, ldr, Y, ldy,
+                              mean, rstd, drop, stream);
 }
 
 int sir_layer_norm_act_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
                            const float* weight, const float* bias, const float* mean, const float* rstd, int act,
                            float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
                            void* stream) {
-    const char* fn = "sir_layer_norm_act_bwd";
-    int rc = check_nodenorm(fn, M, N, 1024, act);
-    if (rc != SIR_OK) return rc;
-    if (ldx < N || ldg < N || lddx < N || ldp < N) return fail(SIR_EINVAL, fn, "leading dimensions must be >= N");
-    if (M == 0) return SIR_OK;
-    if (X == nullptr || dY == nullptr || weight == nullptr || bias == nullptr || mean == nullptr || rstd == nullptr ||
-        dX == nullptr || dw_part == nullptr || db_part == nullptr)
-        return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_layer_norm_act_bwd(X, ldx, dY, ldg, M, (int)N, weight, bias, mean, rstd, act, slope, dX,
-                                                  lddx, dw_part, db_part, ldp, static_cast<hipStream_t>(stream)),
-                  nullptr);
+    return layer_norm_act_bwd("sir_layer_norm_act_bwd", X, ldx, dY, ldg, M, N, weight, bias, mean, rstd, act, slope, dX,
+                              lddx, dw_part, db_part, ldp, nullptr, stream);
+}
+
+int sir_layer_norm_act_drop_bwd(const float* X, int64_t ldx, const float* dY, int64_t ldg, int64_t M, int64_t N,
+                                const float* weight, const float* bias, const float* mean, const float* rstd, int act,
+                                float slope, float* dX, int64_t lddx, float* dw_part, float* db_part, int64_t ldp,
+                                const sir_dropout_t* drop, void* stream) {
+    return layer_norm_act_bwd("sir_layer_norm_act_drop_bwd", X, ldx, dY, ldg, M, N, weight, bias, mean, rstd, act, slope,
+                              dX, lddx, dw_part, db_part, ldp, drop, stream);
 }
 
 // ------------------------------------------------------------------------------ graph readout

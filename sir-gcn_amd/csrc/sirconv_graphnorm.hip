@@ -11,11 +11,15 @@
 // The whole graph is re-read from L2 by each pass (molecule-sized graphs: a few KB), 32 (forward) / 16
 // (backward, two arrays) rows' loads in flight at a time (walk_rows).  One wave per block (spread
 // over the CUs), one column per lane by default (gn_wide below).
+// Layer dropout (DROP instantiations; sirconv_normdrop.h): the forward stores keep(row, col) ? act(y) * scale : +0
+// (+ R), the backward's gate takes act'(y) (keep ? dY * scale : 0); row = the row of X, not the row within its
+// graph, hashed once per row (wave-uniform) and pass.  DROP = false: the kernels without it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_normdrop.h"
 
 namespace sir {
 namespace {
@@ -107,12 +111,13 @@ __device__ __forceinline__ float gn_act_bwd(float y, float g, float slope) {
     else return g;
 }
 
-template <int VW, int ACT>
+template <int VW, int ACT, bool DROP>
 __global__ void __launch_bounds__(64)
 k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
          const float* __restrict__ X, int64_t ldx, const float* __restrict__ w, const float* __restrict__ bias,
          const float* __restrict__ ms, float eps, float slope, const float* __restrict__ R, int64_t ldr,
-         float* __restrict__ Y, int64_t ldy, float* __restrict__ mean_out, float* __restrict__ std_out) {
+         float* __restrict__ Y, int64_t ldy, float* __restrict__ mean_out, float* __restrict__ std_out, Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (wave >= B * n_cc) return;
     const int64_t b = wave / n_cc;
@@ -146,25 +151,28 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
     float sd[VW];
 #pragma unroll
     for (int x = 0; x < VW; ++x) sd[x] = (r1 > r0) ? sqrtf(q[x] / nf + eps) : 0.f;   // norm.py:27
-    auto norm_row = [&](const float (&v)[VW], float (&y)[VW]) {   // norm.py:29, then the activation
+    auto norm_row = [&](int64_t i, const float (&v)[VW], float (&y)[VW]) {   // norm.py:29, then the activation
+        uint32_t rh = 0;
+        if constexpr (DROP) rh = drop_row_hash(drop, i);
 #pragma unroll
         for (int x = 0; x < VW; ++x) {
             const float d = v[x] - t[x];
             y[x] = wv[x] * d / sd[x];
             if (bias) y[x] = y[x] + bv[x];
             y[x] = gn_act<ACT>(y[x], slope);
+            if constexpr (DROP) y[x] = drop_keep(drop, rh, c * VW + x) ? y[x] * drop.scale : 0.f;
         }
     };
     if (R == nullptr) {
         walk_rows<VW>(r0, r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
             float y[VW];
-            norm_row(v, y);
+            norm_row(i, v, y);
             gst<VW>(Y + i * ldy + c * VW, y);
         });
     } else {                                              // + resid (model.py:73)
         walk_rows2<VW>(r0, r1, X, ldx, R, ldr, c, [&](int64_t i, const float (&v)[VW], const float (&r)[VW]) {
             float y[VW];
-            norm_row(v, y);
+            norm_row(i, v, y);
 #pragma unroll
             for (int x = 0; x < VW; ++x) y[x] = y[x] + r[x];
             gst<VW>(Y + i * ldy + c * VW, y);
@@ -176,13 +184,15 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
 
 // ACT: dY is the gradient of act(y); the kernel takes g = act'(y) dY with y = the forward's norm output,
 // recomputed by the forward's own ops (same bits, so the same side of 0)
-template <int VW, int ACT>
+template <int VW, int ACT, bool DROP>
 __global__ void __launch_bounds__(64)
 k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
          const float* __restrict__ X, int64_t ldx, const float* __restrict__ dY, int64_t ldg,
          const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ ms,
          const float* __restrict__ mean, const float* __restrict__ sdv, float slope, float* __restrict__ dX,
-         int64_t lddx, float* __restrict__ dw_part, float* __restrict__ dms_part, float* __restrict__ db_part) {
+         int64_t lddx, float* __restrict__ dw_part, float* __restrict__ dms_part, float* __restrict__ db_part,
+         Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (wave >= B * n_cc) return;
     const int64_t b = wave / n_cc;
@@ -204,21 +214,25 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
 #pragma unroll
     for (int x = 0; x < VW; ++x) { t[x] = ms ? mu[x] * mv[x] : mu[x]; A[x] = 0.f; G[x] = 0.f; Bs[x] = 0.f; }
     // act'(y) dY for the row (y: the forward's norm output, same ops)
-    auto gate = [&](const float (&v)[VW], const float (&g0)[VW], float (&g)[VW]) {
+    auto gate = [&](int64_t i, const float (&v)[VW], const float (&gin)[VW], float (&g)[VW]) {
+        uint32_t rh = 0;
+        if constexpr (DROP) rh = drop_row_hash(drop, i);
 #pragma unroll
         for (int x = 0; x < VW; ++x) {
+            float g0 = gin[x];
+            if constexpr (DROP) g0 = drop_keep(drop, rh, c * VW + x) ? g0 * drop.scale : 0.f;
             if constexpr (ACT == SIR_ACT_IDENTITY) {
-                g[x] = g0[x];
+                g[x] = g0;
             } else {
                 float y = wv[x] * (v[x] - t[x]) / sd[x];
                 if (bias) y = y + bv[x];
-                g[x] = gn_act_bwd<ACT>(y, g0[x], slope);
+                g[x] = gn_act_bwd<ACT>(y, g0, slope);
             }
         }
     };
-    walk_rows2<VW>(r0, r1, X, ldx, dY, ldg, c, [&](int64_t, const float (&v)[VW], const float (&g0)[VW]) {
+    walk_rows2<VW>(r0, r1, X, ldx, dY, ldg, c, [&](int64_t i, const float (&v)[VW], const float (&g0)[VW]) {
         float g[VW];
-        gate(v, g0, g);
+        gate(i, v, g0, g);
 #pragma unroll
         for (int x = 0; x < VW; ++x) { A[x] += g[x] * (v[x] - t[x]); G[x] += g[x]; }
     });
@@ -228,15 +242,15 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         k1[x] = wv[x] / sd[x];                                       // w / s
         k2[x] = wv[x] * A[x] / (nf * sd[x] * sd[x] * sd[x]);          // w A / (n s^3)
     }
-    walk_rows2<VW>(r0, r1, X, ldx, dY, ldg, c, [&](int64_t, const float (&v)[VW], const float (&g0)[VW]) {
+    walk_rows2<VW>(r0, r1, X, ldx, dY, ldg, c, [&](int64_t i, const float (&v)[VW], const float (&g0)[VW]) {
         float g[VW];
-        gate(v, g0, g);
+        gate(i, v, g0, g);
 #pragma unroll
         for (int x = 0; x < VW; ++x) Bs[x] += k1[x] * g[x] - k2[x] * (v[x] - t[x]);
     });
     walk_rows2<VW>(r0, r1, X, ldx, dY, ldg, c, [&](int64_t i, const float (&v)[VW], const float (&g0)[VW]) {
         float g[VW];
-        gate(v, g0, g);
+        gate(i, v, g0, g);
         float o[VW];
 #pragma unroll
         for (int x = 0; x < VW; ++x) o[x] = (k1[x] * g[x] - k2[x] * (v[x] - t[x])) - mv[x] * Bs[x] / nf;
@@ -267,22 +281,26 @@ bool gn_wide(int64_t, int) {
 
 }  // namespace
 
-template <int ACT>
-static void launch_gn_fwd(bool v4, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int F, int n_cc,
-                          const float* X, int64_t ldx, const float* w, const float* bias, const float* ms, float eps,
-                          float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd) {
+
+namespace {
+
+template <int ACT, bool DROP>
+void launch_gn_fwd(bool v4, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int F, int n_cc,
+                   const float* X, int64_t ldx, const float* w, const float* bias, const float* ms, float eps,
+                   float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd,
+                   const Drop& drop) {
     if (v4)
-        hipLaunchKernelGGL((k_gn_fwd<4, ACT>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w, bias, ms,
-                           eps, slope, R, ldr, Y, ldy, mean, sd);
+        hipLaunchKernelGGL((k_gn_fwd<4, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w, bias, ms,
+                           eps, slope, R, ldr, Y, ldy, mean, sd, drop);
     else
-        hipLaunchKernelGGL((k_gn_fwd<1, ACT>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w, bias, ms,
-                           eps, slope, R, ldr, Y, ldy, mean, sd);
+        hipLaunchKernelGGL((k_gn_fwd<1, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w, bias, ms,
+                           eps, slope, R, ldr, Y, ldy, mean, sd, drop);
 }
 
-hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
-                              const float* w, const float* bias, const float* ms, float eps, int act, float slope,
-                              const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd,
-                              hipStream_t st) {
+template <bool DROP>
+hipError_t gn_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* w, const float* bias,
+                  const float* ms, float eps, int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
+                  float* mean, float* sd, const Drop& drop, hipStream_t st) {
     if (B == 0) return hipSuccess;
     const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
                     al(R) && al(w) && al(bias) && al(ms) && al(mean) && al(sd) && gn_wide(B, F);
@@ -291,37 +309,40 @@ hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float*
     const unsigned blocks = (unsigned)(B * n_cc);
     switch (act) {
     case SIR_ACT_IDENTITY:
-        launch_gn_fwd<SIR_ACT_IDENTITY>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y, ldy, mean, sd);
+        launch_gn_fwd<SIR_ACT_IDENTITY, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y,
+                                              ldy, mean, sd, drop);
         break;
     case SIR_ACT_RELU:
-        launch_gn_fwd<SIR_ACT_RELU>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y, ldy, mean, sd);
+        launch_gn_fwd<SIR_ACT_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y, ldy,
+                                          mean, sd, drop);
         break;
     case SIR_ACT_LEAKY_RELU:
-        launch_gn_fwd<SIR_ACT_LEAKY_RELU>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y, ldy,
-                                          mean, sd);
+        launch_gn_fwd<SIR_ACT_LEAKY_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr,
+                                                Y, ldy, mean, sd, drop);
         break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-template <int ACT>
-static void launch_gn_bwd(bool v4, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int F, int n_cc,
-                          const float* X, int64_t ldx, const float* dY, int64_t ldg, const float* w, const float* bias,
-                          const float* ms, const float* mean, const float* sd, float slope, float* dX, int64_t lddx,
-                          float* dw_part, float* dms_part, float* db_part) {
+template <int ACT, bool DROP>
+void launch_gn_bwd(bool v4, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int F, int n_cc,
+                   const float* X, int64_t ldx, const float* dY, int64_t ldg, const float* w, const float* bias,
+                   const float* ms, const float* mean, const float* sd, float slope, float* dX, int64_t lddx,
+                   float* dw_part, float* dms_part, float* db_part, const Drop& drop) {
     if (v4)
-        hipLaunchKernelGGL((k_gn_bwd<4, ACT>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias,
-                           ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part);
+        hipLaunchKernelGGL((k_gn_bwd<4, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY, ldg, w,
+                           bias, ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part, drop);
     else
-        hipLaunchKernelGGL((k_gn_bwd<1, ACT>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias,
-                           ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part);
+        hipLaunchKernelGGL((k_gn_bwd<1, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY, ldg, w,
+                           bias, ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part, drop);
 }
 
-hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
-                              const float* dY, int64_t ldg, const float* w, const float* bias, const float* ms,
-                              const float* mean, const float* sd, int act, float slope, float* dX, int64_t lddx,
-                              float* dw_part, float* dms_part, float* db_part, hipStream_t st) {
+template <bool DROP>
+hipError_t gn_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* dY, int64_t ldg,
+                  const float* w, const float* bias, const float* ms, const float* mean, const float* sd, int act,
+                  float slope, float* dX, int64_t lddx, float* dw_part, float* dms_part, float* db_part,
+                  const Drop& drop, hipStream_t st) {
     if (B == 0) return hipSuccess;
     const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && al(X) && al(dY) && al(dX) &&
                     al(w) && al(bias) && al(ms) && al(mean) && al(sd) && al(dw_part) && al(dms_part) && al(db_part) &&
@@ -331,20 +352,57 @@ hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float*
     const unsigned blocks = (unsigned)(B * n_cc);
     switch (act) {
     case SIR_ACT_IDENTITY:
-        launch_gn_bwd<SIR_ACT_IDENTITY>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd, slope, dX,
-                                        lddx, dw_part, dms_part, db_part);
+        launch_gn_bwd<SIR_ACT_IDENTITY, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd,
+                                              slope, dX, lddx, dw_part, dms_part, db_part, drop);
         break;
     case SIR_ACT_RELU:
-        launch_gn_bwd<SIR_ACT_RELU>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd, slope, dX,
-                                    lddx, dw_part, dms_part, db_part);
+        launch_gn_bwd<SIR_ACT_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd, slope,
+                                          dX, lddx, dw_part, dms_part, db_part, drop);
         break;
     case SIR_ACT_LEAKY_RELU:
-        launch_gn_bwd<SIR_ACT_LEAKY_RELU>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd, slope,
-                                          dX, lddx, dw_part, dms_part, db_part);
+        launch_gn_bwd<SIR_ACT_LEAKY_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd,
+                                                slope, dX, lddx, dw_part, dms_part, db_part, drop);
         break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
+                              const float* w, const float* bias, const float* ms, float eps, int act, float slope,
+                              const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd,
+                              hipStream_t st) {
+    return gn_fwd<false>(off, B, F, X, ldx, w, bias, ms, eps, act, slope, R, ldr, Y, ldy, mean, sd, Drop(), st);
+}
+
+hipError_t run_graph_norm_drop_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* w,
+                                   const float* bias, const float* ms, float eps, int act, float slope, const float* R,
+                                   int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd, const Drop& drop,
+                                   hipStream_t st) {
+    if (!drop.on())
+        return gn_fwd<false>(off, B, F, X, ldx, w, bias, ms, eps, act, slope, R, ldr, Y, ldy, mean, sd, Drop(), st);
+    return gn_fwd<true>(off, B, F, X, ldx, w, bias, ms, eps, act, slope, R, ldr, Y, ldy, mean, sd, drop, st);
+}
+
+hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
+                              const float* dY, int64_t ldg, const float* w, const float* bias, const float* ms,
+                              const float* mean, const float* sd, int act, float slope, float* dX, int64_t lddx,
+                              float* dw_part, float* dms_part, float* db_part, hipStream_t st) {
+    return gn_bwd<false>(off, B, F, X, ldx, dY, ldg, w, bias, ms, mean, sd, act, slope, dX, lddx, dw_part, dms_part,
+                         db_part, Drop(), st);
+}
+
+hipError_t run_graph_norm_drop_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* dY,
+                                   int64_t ldg, const float* w, const float* bias, const float* ms, const float* mean,
+                                   const float* sd, int act, float slope, float* dX, int64_t lddx, float* dw_part,
+                                   float* dms_part, float* db_part, const Drop& drop, hipStream_t st) {
+    if (!drop.on())
+        return gn_bwd<false>(off, B, F, X, ldx, dY, ldg, w, bias, ms, mean, sd, act, slope, dX, lddx, dw_part, dms_part,
+                             db_part, Drop(), st);
+    return gn_bwd<true>(off, B, F, X, ldx, dY, ldg, w, bias, ms, mean, sd, act, slope, dX, lddx, dw_part, dms_part,
+                        db_part, drop, st);
 }
 
 }  // namespace sir

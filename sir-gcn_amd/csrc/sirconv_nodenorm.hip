@@ -26,11 +26,16 @@
 //   k_ln_bwd      g = act'(y) D;  dX = rstd * (g gamma - mean_row(g gamma) - xhat * mean_row(g gamma xhat));
 //                 the wave's rows' sum g * xhat, sum g as one partial row (summed by the deterministic
 //                 column sum, run_colsum).
+// Layer dropout (DROP instantiations; sirconv_normdrop.h): out = drop(act(y)) + R, drop(a) = keep(row, col) ? a * scale : +0
+// with the bits of sirconv_dropout.h at col0 = 0 (the row hash once per row and thread, one fmix per element); every
+// backward kernel takes g = act'(y) (keep ? D * scale : 0) wherever it took act'(y) D.  The DROP = false
+// instantiations are the kernels without it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_normdrop.h"
 
 namespace sir {
 namespace {
@@ -247,12 +252,13 @@ __device__ __forceinline__ void bn_cols(double (&mu)[VW], double (&a)[VW], doubl
     }
 }
 
-template <int VW, int ACT>
+template <int VW, int ACT, bool DROP>
 __global__ void __launch_bounds__(BN_THREADS)
 k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, int rs,
            const double* __restrict__ mean, const double* __restrict__ invstd, const float* __restrict__ gamma,
            const float* __restrict__ beta, float slope, const float* __restrict__ R, int64_t ldr,
-           float* __restrict__ Y, int64_t ldy) {
+           float* __restrict__ Y, int64_t ldy, Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     const BnPos p = bn_pos(cwv, rs, N / VW);
     if (!p.on) return;
     const int64_t r0 = (int64_t)blockIdx.x * SLAB;
@@ -273,10 +279,13 @@ k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
             const int64_t row = base + (int64_t)k * rs;
             if (row < r1) {
                 float o[VW];
+                uint32_t rh = 0;
+                if constexpr (DROP) rh = drop_row_hash(drop, row);
 #pragma unroll
                 for (int x = 0; x < VW; ++x) {
                     const float y = (float)(((double)v[k][x] - mu[x]) * a[x] + b[x]);
                     o[x] = nn_act<ACT>(y, slope);
+                    if constexpr (DROP) o[x] = drop_keep(drop, rh, (int)col + x) ? o[x] * drop.scale : 0.f;
                     if (R != nullptr) o[x] = o[x] + r[k][x];
                 }
                 nst<VW>(Y + row * ldy + col, o);
@@ -286,12 +295,13 @@ k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
 }
 
 // per slab: sum g and sum g (x - mean) (fp64), g = act'(y) D, y by k_bn_apply's own ops
-template <int VW, int ACT>
+template <int VW, int ACT, bool DROP>
 __global__ void __launch_bounds__(BN_THREADS)
 k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, int64_t ldg, int64_t M, int N,
              int cwv, int rs, const double* __restrict__ mean, const double* __restrict__ invstd,
              const float* __restrict__ gamma, const float* __restrict__ beta, float slope,
-             double* __restrict__ pdb, double* __restrict__ pdg) {
+             double* __restrict__ pdb, double* __restrict__ pdg, Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     __shared__ double s_b[BN_THREADS][VW];
     __shared__ double s_g[BN_THREADS][VW];
     const BnPos p = bn_pos(cwv, rs, N / VW);
@@ -315,11 +325,15 @@ k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (base + (int64_t)k * rs < r1) {
+                    uint32_t rh = 0;
+                    if constexpr (DROP) rh = drop_row_hash(drop, base + (int64_t)k * rs);
 #pragma unroll
                     for (int x = 0; x < VW; ++x) {
                         const double c = (double)v[k][x] - mu[x];
                         const float y = (float)(c * a[x] + b[x]);
-                        const float gg = nn_act_bwd<ACT>(y, d[k][x], slope);
+                        float g0 = d[k][x];
+                        if constexpr (DROP) g0 = drop_keep(drop, rh, (int)col + x) ? g0 * drop.scale : 0.f;
+                        const float gg = nn_act_bwd<ACT>(y, g0, slope);
                         sb[x] += (double)gg;
                         sg[x] += (double)gg * c;
                     }
@@ -346,13 +360,14 @@ k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__
 
 // training: dX = ((g - gm) - (x - mean) k) invstd gamma, gm = sum g / M, k = dotp invstd^2 / M (fp64, rounded
 // once); eval: dX = g invstd gamma
-template <int VW, int ACT>
+template <int VW, int ACT, bool DROP>
 __global__ void __launch_bounds__(BN_THREADS)
 k_bn_bwd_app(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, int64_t ldg, int64_t M, int N,
              int cwv, int rs, const double* __restrict__ mean, const double* __restrict__ invstd,
              const float* __restrict__ gamma, const float* __restrict__ beta, float slope,
              const double* __restrict__ gmean, const double* __restrict__ kdot, int training,
-             float* __restrict__ dX, int64_t lddx) {
+             float* __restrict__ dX, int64_t lddx, Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     const BnPos p = bn_pos(cwv, rs, N / VW);
     if (!p.on) return;
     const int64_t r0 = (int64_t)blockIdx.x * SLAB;
@@ -378,11 +393,15 @@ k_bn_bwd_app(const float* __restrict__ X, int64_t ldx, const float* __restrict__
             const int64_t row = base + (int64_t)k * rs;
             if (row < r1) {
                 float o[VW];
+                uint32_t rh = 0;
+                if constexpr (DROP) rh = drop_row_hash(drop, row);
 #pragma unroll
                 for (int x = 0; x < VW; ++x) {
                     const double c = (double)v[k][x] - mu[x];
                     const float y = (float)(c * a[x] + b[x]);
-                    const float gg = nn_act_bwd<ACT>(y, d[k][x], slope);
+                    float g0 = d[k][x];
+                    if constexpr (DROP) g0 = drop_keep(drop, rh, (int)col + x) ? g0 * drop.scale : 0.f;
+                    const float gg = nn_act_bwd<ACT>(y, g0, slope);
                     o[x] = (float)((((double)gg - gm[x]) - c * kk[x]) * a[x]);
                 }
                 nst<VW>(dX + row * lddx + col, o);
@@ -404,11 +423,12 @@ constexpr int ln_rb(int vw, int nch, int cap) {
     return r < 1 ? 1 : (r > 4 ? 4 : r);
 }
 
-template <int VW, int NCH, int ACT>
+template <int VW, int NCH, int ACT, bool DROP>
 __global__ void __launch_bounds__(64)
 k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw, const float* __restrict__ gamma,
          const float* __restrict__ beta, float eps, float slope, const float* __restrict__ R, int64_t ldr,
-         float* __restrict__ Y, int64_t ldy, float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+         float* __restrict__ Y, int64_t ldy, float* __restrict__ mean_out, float* __restrict__ rstd_out, Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     constexpr int RB = ln_rb(VW, NCH, 16);
     const int lane = (int)threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * rpw;
@@ -457,6 +477,8 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
             }
             const float rstd = 1.0f / sqrtf(wave_sum(q) / nf + eps);
             if (r + k < r1) {
+                uint32_t rh = 0;                                   // wave-uniform: the row is the wave's
+                if constexpr (DROP) rh = drop_row_hash(drop, r + k);
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) {
                     if (on[j]) {
@@ -465,6 +487,8 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
                         for (int x = 0; x < VW; ++x) {
                             const float y = (v[k][j][x] - mu) * rstd * g[j][x] + b[j][x];
                             o[x] = nn_act<ACT>(y, slope);
+                            if constexpr (DROP)
+                                o[x] = drop_keep(drop, rh, (j * 64 + lane) * VW + x) ? o[x] * drop.scale : 0.f;
                             if (R != nullptr) o[x] = o[x] + rr[k][j][x];
                         }
                         nst<VW>(Y + (r + k) * ldy + (j * 64 + lane) * VW, o);
@@ -476,12 +500,13 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
     }
 }
 
-template <int VW, int NCH, int ACT>
+template <int VW, int NCH, int ACT, bool DROP>
 __global__ void __launch_bounds__(64)
 k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, int64_t ldg, int64_t M, int N,
          int64_t rpw, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
          const float* __restrict__ rstd, float slope, float* __restrict__ dX, int64_t lddx,
-         float* __restrict__ dw_part, float* __restrict__ db_part, int64_t ldp) {
+         float* __restrict__ dw_part, float* __restrict__ db_part, int64_t ldp, Drop drop) {
+    if constexpr (DROP) drop = drop_resolve(drop);
     constexpr int RB = ln_rb(VW, NCH, 8);
     const int lane = (int)threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * rpw;
@@ -519,13 +544,17 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
             if (r + k < r1) {                                      // wave-uniform
                 float xh[NCH][VW], a[NCH][VW];
                 float s1 = 0.f, s2 = 0.f;
+                uint32_t rh = 0;
+                if constexpr (DROP) rh = drop_row_hash(drop, r + k);
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) {
 #pragma unroll
                     for (int x = 0; x < VW; ++x) {
                         xh[j][x] = (v[k][j][x] - mu[k]) * rs[k];
                         const float y = xh[j][x] * g[j][x] + b[j][x];
-                        const float gg = on[j] ? nn_act_bwd<ACT>(y, d[k][j][x], slope) : 0.f;
+                        float g0 = d[k][j][x];
+                        if constexpr (DROP) g0 = drop_keep(drop, rh, (j * 64 + lane) * VW + x) ? g0 * drop.scale : 0.f;
+                        const float gg = on[j] ? nn_act_bwd<ACT>(y, g0, slope) : 0.f;
                         db[j][x] += gg;
                         dw[j][x] += gg * xh[j][x];
                         a[j][x] = gg * g[j][x];
@@ -608,29 +637,34 @@ hipError_t run_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int N, f
     return hipGetLastError();
 }
 
-hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
-                                  const double* invstd, const float* gamma, const float* beta, int act, float slope,
-                                  const float* R, int64_t ldr, float* Y, int64_t ldy, hipStream_t st) {
+
+namespace {
+
+template <bool DROP>
+hipError_t bn_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean, const double* invstd,
+                      const float* gamma, const float* beta, int act, float slope, const float* R, int64_t ldr,
+                      float* Y, int64_t ldy, const Drop& drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
     const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
                     al(R);
     const BnGeom g = bn_geom(M, N, v4);
 #define CALL(A)                                                                                                        \
     if (v4)                                                                                                            \
-        hipLaunchKernelGGL((k_bn_apply<4, A>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, mean, invstd, \
-                           gamma, beta, slope, R, ldr, Y, ldy);                                                        \
+        hipLaunchKernelGGL((k_bn_apply<4, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, mean,  \
+                           invstd, gamma, beta, slope, R, ldr, Y, ldy, drop);                                          \
     else                                                                                                               \
-        hipLaunchKernelGGL((k_bn_apply<1, A>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, mean, invstd, \
-                           gamma, beta, slope, R, ldr, Y, ldy)
+        hipLaunchKernelGGL((k_bn_apply<1, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, mean,  \
+                           invstd, gamma, beta, slope, R, ldr, Y, ldy, drop)
     SIR_NN_ACT_SWITCH(act, CALL)
 #undef CALL
     return hipGetLastError();
 }
 
-hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                  const double* mean, const double* invstd, const float* gamma, const float* beta,
-                                  int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
-                                  float* dbeta, float* work, hipStream_t st) {
+template <bool DROP>
+hipError_t bn_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N, const double* mean,
+                      const double* invstd, const float* gamma, const float* beta, int act, float slope, int training,
+                      float* dX, int64_t lddx, float* dgamma, float* dbeta, float* work, const Drop& drop,
+                      hipStream_t st) {
     if (M == 0) return hipSuccess;
     const int64_t S = batch_norm_slabs(M);
     double* pdb = reinterpret_cast<double*>(work);
@@ -641,11 +675,11 @@ hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, i
     const BnGeom g = bn_geom(M, N, v4);
 #define CALL(A)                                                                                                        \
     if (v4)                                                                                                            \
-        hipLaunchKernelGGL((k_bn_bwd_red<4, A>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv, g.rs,    \
-                           mean, invstd, gamma, beta, slope, pdb, pdg);                                                \
+        hipLaunchKernelGGL((k_bn_bwd_red<4, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
+                           g.rs, mean, invstd, gamma, beta, slope, pdb, pdg, drop);                                    \
     else                                                                                                               \
-        hipLaunchKernelGGL((k_bn_bwd_red<1, A>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv, g.rs,    \
-                           mean, invstd, gamma, beta, slope, pdb, pdg)
+        hipLaunchKernelGGL((k_bn_bwd_red<1, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
+                           g.rs, mean, invstd, gamma, beta, slope, pdb, pdg, drop)
     SIR_NN_ACT_SWITCH(act, CALL)
 #undef CALL
     hipLaunchKernelGGL((k_bn_finish<false>), dim3((unsigned)((N + FIN_COLS - 1) / FIN_COLS)),
@@ -653,14 +687,49 @@ hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, i
                        dgamma, gmean, kdot);
 #define CALL(A)                                                                                                        \
     if (v4)                                                                                                            \
-        hipLaunchKernelGGL((k_bn_bwd_app<4, A>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv, g.rs,    \
-                           mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx);                         \
+        hipLaunchKernelGGL((k_bn_bwd_app<4, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
+                           g.rs, mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx, drop);             \
     else                                                                                                               \
-        hipLaunchKernelGGL((k_bn_bwd_app<1, A>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv, g.rs,    \
-                           mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx)
+        hipLaunchKernelGGL((k_bn_bwd_app<1, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
+                           g.rs, mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx, drop)
     SIR_NN_ACT_SWITCH(act, CALL)
 #undef CALL
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
+                                  const double* invstd, const float* gamma, const float* beta, int act, float slope,
+                                  const float* R, int64_t ldr, float* Y, int64_t ldy, hipStream_t st) {
+    return bn_act_fwd<false>(X, ldx, M, N, mean, invstd, gamma, beta, act, slope, R, ldr, Y, ldy, Drop(), st);
+}
+
+hipError_t run_batch_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
+                                       const double* invstd, const float* gamma, const float* beta, int act,
+                                       float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
+                                       const Drop& drop, hipStream_t st) {
+    if (!drop.on()) return bn_act_fwd<false>(X, ldx, M, N, mean, invstd, gamma, beta, act, slope, R, ldr, Y, ldy, Drop(), st);
+    return bn_act_fwd<true>(X, ldx, M, N, mean, invstd, gamma, beta, act, slope, R, ldr, Y, ldy, drop, st);
+}
+
+hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                  const double* mean, const double* invstd, const float* gamma, const float* beta,
+                                  int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
+                                  float* dbeta, float* work, hipStream_t st) {
+    return bn_act_bwd<false>(X, ldx, D, ldg, M, N, mean, invstd, gamma, beta, act, slope, training, dX, lddx, dgamma,
+                             dbeta, work, Drop(), st);
+}
+
+hipError_t run_batch_norm_act_drop_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                       const double* mean, const double* invstd, const float* gamma, const float* beta,
+                                       int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
+                                       float* dbeta, float* work, const Drop& drop, hipStream_t st) {
+    if (!drop.on())
+        return bn_act_bwd<false>(X, ldx, D, ldg, M, N, mean, invstd, gamma, beta, act, slope, training, dX, lddx, dgamma,
+                                 dbeta, work, Drop(), st);
+    return bn_act_bwd<true>(X, ldx, D, ldg, M, N, mean, invstd, gamma, beta, act, slope, training, dX, lddx, dgamma,
+                            dbeta, work, drop, st);
 }
 
 // rows per wave (= per partial row of the backward): a function of M alone
@@ -676,13 +745,13 @@ int64_t layer_norm_parts(int64_t M) {
 namespace {
 
 // NCH: float4 rows 1, 2 or 4 vectors per lane (N <= 256, 512, 1024); scalar rows 1, 2, 4, 8 or 16
-template <int ACT>
+template <int ACT, bool DROP>
 hipError_t launch_ln_fwd(bool v4, int N, unsigned blocks, hipStream_t st, const float* X, int64_t ldx, int64_t M,
                          int64_t rpw, const float* gamma, const float* beta, float eps, float slope, const float* R,
-                         int64_t ldr, float* Y, int64_t ldy, float* mean, float* rstd) {
+                         int64_t ldr, float* Y, int64_t ldy, float* mean, float* rstd, const Drop& drop) {
 #define LNF(VW, NCH)                                                                                                  \
-    hipLaunchKernelGGL((k_ln_fwd<VW, NCH, ACT>), dim3(blocks), dim3(64), 0, st, X, ldx, M, N, rpw, gamma, beta, eps,  \
-                       slope, R, ldr, Y, ldy, mean, rstd)
+    hipLaunchKernelGGL((k_ln_fwd<VW, NCH, ACT, DROP>), dim3(blocks), dim3(64), 0, st, X, ldx, M, N, rpw, gamma, beta, \
+                       eps, slope, R, ldr, Y, ldy, mean, rstd, drop)
     if (v4) {
         if (N <= 256) LNF(4, 1);
         else if (N <= 512) LNF(4, 2);
@@ -698,14 +767,14 @@ hipError_t launch_ln_fwd(bool v4, int N, unsigned blocks, hipStream_t st, const 
     return hipGetLastError();
 }
 
-template <int ACT>
+template <int ACT, bool DROP>
 hipError_t launch_ln_bwd(bool v4, int N, unsigned blocks, hipStream_t st, const float* X, int64_t ldx, const float* D,
                          int64_t ldg, int64_t M, int64_t rpw, const float* gamma, const float* beta, const float* mean,
                          const float* rstd, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
-                         int64_t ldp) {
+                         int64_t ldp, const Drop& drop) {
 #define LNB(VW, NCH)                                                                                                  \
-    hipLaunchKernelGGL((k_ln_bwd<VW, NCH, ACT>), dim3(blocks), dim3(64), 0, st, X, ldx, D, ldg, M, N, rpw, gamma,     \
-                       beta, mean, rstd, slope, dX, lddx, dw_part, db_part, ldp)
+    hipLaunchKernelGGL((k_ln_bwd<VW, NCH, ACT, DROP>), dim3(blocks), dim3(64), 0, st, X, ldx, D, ldg, M, N, rpw,      \
+                       gamma, beta, mean, rstd, slope, dX, lddx, dw_part, db_part, ldp, drop)
     if (v4) {
         if (N <= 256) LNB(4, 1);
         else if (N <= 512) LNB(4, 2);
@@ -721,37 +790,74 @@ hipError_t launch_ln_bwd(bool v4, int N, unsigned blocks, hipStream_t st, const 
     return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t run_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
-                                  const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
-                                  float* Y, int64_t ldy, float* mean, float* rstd, hipStream_t st) {
+template <bool DROP>
+hipError_t ln_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma, const float* beta, float eps,
+                      int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean,
+                      float* rstd, const Drop& drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
     const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
                     al(R) && al(gamma) && al(beta);
     const int64_t rpw = layer_norm_rows_per_part(M);
     const unsigned blocks = (unsigned)layer_norm_parts(M);
-#define CALL(A) return launch_ln_fwd<A>(v4, N, blocks, st, X, ldx, M, rpw, gamma, beta, eps, slope, R, ldr, Y, ldy, mean, rstd)
+#define CALL(A)                                                                                                        \
+    return launch_ln_fwd<A, DROP>(v4, N, blocks, st, X, ldx, M, rpw, gamma, beta, eps, slope, R, ldr, Y, ldy, mean, rstd, \
+                                  drop)
     SIR_NN_ACT_SWITCH(act, CALL)
 #undef CALL
     return hipSuccess;
 }
 
-hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                  const float* gamma, const float* beta, const float* mean, const float* rstd,
-                                  int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
-                                  int64_t ldp, hipStream_t st) {
+template <bool DROP>
+hipError_t ln_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N, const float* gamma,
+                      const float* beta, const float* mean, const float* rstd, int act, float slope, float* dX,
+                      int64_t lddx, float* dw_part, float* db_part, int64_t ldp, const Drop& drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
     const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && ldp % 4 == 0 && al(X) && al(D) &&
                     al(dX) && al(gamma) && al(beta) && al(dw_part) && al(db_part);
     const int64_t rpw = layer_norm_rows_per_part(M);
     const unsigned blocks = (unsigned)layer_norm_parts(M);
 #define CALL(A)                                                                                                        \
-    return launch_ln_bwd<A>(v4, N, blocks, st, X, ldx, D, ldg, M, rpw, gamma, beta, mean, rstd, slope, dX, lddx, dw_part, \
-                            db_part, ldp)
+    return launch_ln_bwd<A, DROP>(v4, N, blocks, st, X, ldx, D, ldg, M, rpw, gamma, beta, mean, rstd, slope, dX, lddx,  \
+                                  dw_part, db_part, ldp, drop)
     SIR_NN_ACT_SWITCH(act, CALL)
 #undef CALL
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t run_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
+                                  const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
+                                  float* Y, int64_t ldy, float* mean, float* rstd, hipStream_t st) {
+    return ln_act_fwd<false>(X, ldx, M, N, gamma, beta, eps, act, slope, R, ldr, Y, ldy, mean, rstd, Drop(), st);
+}
+
+hipError_t run_layer_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
+                                       const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
+                                       float* Y, int64_t ldy, float* mean, float* rstd, const Drop& drop,
+                                       hipStream_t st) {
+    if (!drop.on())
+        return ln_act_fwd<false>(X, ldx, M, N, gamma, beta, eps, act, slope, R, ldr, Y, ldy, mean, rstd, Drop(), st);
+    return ln_act_fwd<true>(X, ldx, M, N, gamma, beta, eps, act, slope, R, ldr, Y, ldy, mean, rstd, drop, st);
+}
+
+hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                  const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                  int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
+                                  int64_t ldp, hipStream_t st) {
+    return ln_act_bwd<false>(X, ldx, D, ldg, M, N, gamma, beta, mean, rstd, act, slope, dX, lddx, dw_part, db_part, ldp,
+                             Drop(), st);
+}
+
+hipError_t run_layer_norm_act_drop_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                       const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                       int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
+                                       int64_t ldp, const Drop& drop, hipStream_t st) {
+    if (!drop.on())
+        return ln_act_bwd<false>(X, ldx, D, ldg, M, N, gamma, beta, mean, rstd, act, slope, dX, lddx, dw_part, db_part,
+                                 ldp, Drop(), st);
+    return ln_act_bwd<true>(X, ldx, D, ldg, M, N, gamma, beta, mean, rstd, act, slope, dX, lddx, dw_part, db_part, ldp,
+                            drop, st);
 }
 
 }  // namespace sir

@@ -49,6 +49,19 @@ SIGNATURES = {
                                               _P]),
     "sir_layer_norm_act_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _P,
                                               _P, _I64, _P]),
+    # the *_act_* signatures with a trailing sir_dropout_t* before the stream
+    "sir_graph_norm_act_drop_fwd": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P, _F, _I, _F, _P, _I64, _P,
+                                                   _I64, _P, _P, _P, _P]),
+    "sir_graph_norm_act_drop_bwd": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I, _F,
+                                                   _P, _I64, _P, _P, _P, _P, _P]),
+    "sir_batch_norm_act_drop_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _P, _I64,
+                                                   _P, _P]),
+    "sir_batch_norm_act_drop_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _I, _P,
+                                                   _I64, _P, _P, _P, _P, _P]),
+    "sir_layer_norm_act_drop_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _P, _F, _I, _F, _P, _I64, _P, _I64, _P,
+                                                   _P, _P, _P]),
+    "sir_layer_norm_act_drop_bwd": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64,
+                                                   _P, _P, _I64, _P, _P]),
     "sir_graph_pool_slab_rows": (ctypes.c_int64, []),
     "sir_graph_pool_work_floats": (ctypes.c_int64, [_I64, _I64, _I64, _I]),
     "sir_graph_pool_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _I64, _P, _P, _P]),
@@ -550,6 +563,32 @@ def graph_norm_act_bwd(off, X, dY, weight, bias, mean_scale, mean, std, act, slo
     _check(rc, lib)
 
 
+def graph_norm_act_drop_fwd(off, X, weight, bias, mean_scale, eps, act, slope, R, Y, mean, std, drop):
+    """GraphNorm -> act -> layer dropout -> + R in one kernel (``sir_graph_norm_act_drop_fwd``); ``drop`` =
+    (seed, p) as for :func:`dropout_apply`, the bits of an [V, F] block at col0 = 0."""
+    lib = load()
+    B, F = mean.shape
+    with _Timed("sir_graph_norm_fwd", Y.device):
+        rc = lib.sir_graph_norm_act_drop_fwd(_ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(weight), _ptr(bias),
+                                             _ptr(mean_scale), float(eps), int(act), float(slope), _ptr(R),
+                                             _ld(R, F) if R is not None else 0, _ptr(Y), _ld(Y, F), _ptr(mean),
+                                             _ptr(std), _drop(drop), _stream(Y.device))
+    _check(rc, lib)
+
+
+def graph_norm_act_drop_bwd(off, X, dY, weight, bias, mean_scale, mean, std, act, slope, dX, dw_part, dms_part, db_part,
+                            drop):
+    """Backward of :func:`graph_norm_act_drop_fwd` (the same ``drop``: the mask is recomputed)."""
+    lib = load()
+    B, F = mean.shape
+    with _Timed("sir_graph_norm_bwd", dX.device):
+        rc = lib.sir_graph_norm_act_drop_bwd(_ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(dY), _ld(dY, F), _ptr(weight),
+                                             _ptr(bias), _ptr(mean_scale), _ptr(mean), _ptr(std), int(act),
+                                             float(slope), _ptr(dX), _ld(dX, F), _ptr(dw_part), _ptr(dms_part),
+                                             _ptr(db_part), _drop(drop), _stream(dX.device))
+    _check(rc, lib)
+
+
 def graph_norm_bwd(off, X, dY, weight, mean_scale, mean, std, dX, dw_part, dms_part, db_part):
     lib = load()
     B, F = mean.shape
@@ -603,6 +642,31 @@ def batch_norm_act_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, 
                                         _ptr(weight), _ptr(bias), int(act), float(slope), int(bool(training)),
                                         _ptr(dX), _ld(dX, N), _ptr(dweight), _ptr(dbias), _ptr(work),
                                         _stream(X.device))
+    _check(rc, lib)
+
+
+def batch_norm_act_drop_fwd(X, mean, invstd, weight, bias, act, slope, R, Y, drop):
+    """:func:`batch_norm_act_fwd` with the layer dropout between the activation and the add of R
+    (``sir_batch_norm_act_drop_fwd``); ``drop`` = (seed, p), the bits of an [M, N] block at col0 = 0."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_batch_norm_act_fwd", X.device):
+        rc = lib.sir_batch_norm_act_drop_fwd(_ptr(X), _ld(X, N), M, N, _ptr(mean), _ptr(invstd), _ptr(weight),
+                                             _ptr(bias), int(act), float(slope), _ptr(R),
+                                             _ld(R, N) if R is not None else 0, _ptr(Y), _ld(Y, N), _drop(drop),
+                                             _stream(X.device))
+    _check(rc, lib)
+
+
+def batch_norm_act_drop_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, dX, dweight, dbias, work, drop):
+    """Backward of :func:`batch_norm_act_drop_fwd` (the same ``drop``: the mask is recomputed)."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_batch_norm_act_bwd", X.device):
+        rc = lib.sir_batch_norm_act_drop_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(mean), _ptr(invstd),
+                                             _ptr(weight), _ptr(bias), int(act), float(slope), int(bool(training)),
+                                             _ptr(dX), _ld(dX, N), _ptr(dweight), _ptr(dbias), _ptr(work),
+                                             _drop(drop), _stream(X.device))
     _check(rc, lib)
 
 
@@ -701,6 +765,38 @@ def layer_norm_act_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX):
                                         _ptr(part), _ptr(db_part), 2 * npad, _stream(X.device))
     _check(rc, lib)
     tot = col_sum(part[:parts])             # (the pad columns of an N % 4 != 0 row are summed and dropped)
+    return tot[:N], tot[npad:npad + N]
+
+
+def layer_norm_act_drop_fwd(X, weight, bias, eps, act, slope, R, Y, mean, rstd, drop):
+    """:func:`layer_norm_act_fwd` with the layer dropout between the activation and the add of R
+    (``sir_layer_norm_act_drop_fwd``); ``drop`` = (seed, p), the bits of an [M, N] block at col0 = 0."""
+    lib = load()
+    M, N = X.shape
+    with _Timed("sir_layer_norm_act_fwd", X.device):
+        rc = lib.sir_layer_norm_act_drop_fwd(_ptr(X), _ld(X, N), M, N, _ptr(weight), _ptr(bias), float(eps), int(act),
+                                             float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y),
+                                             _ld(Y, N), _ptr(mean), _ptr(rstd), _drop(drop), _stream(X.device))
+    _check(rc, lib)
+
+
+def layer_norm_act_drop_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX, drop):
+    """Backward of :func:`layer_norm_act_drop_fwd` (the same ``drop``); returns (dweight, dbias) as
+    :func:`layer_norm_act_bwd`."""
+    lib = load()
+    M, N = X.shape
+    parts = int(lib.sir_layer_norm_bwd_parts(M, N))
+    if parts < 0:
+        raise RuntimeError(f"sir_layer_norm_bwd_parts({M}, {N}): sizes out of range")
+    npad = (N + 3) // 4 * 4
+    part = torch.empty((max(parts, 1), 2 * npad), device=X.device, dtype=torch.float32)
+    db_part = part[:, npad:]
+    with _Timed("sir_layer_norm_act_bwd", X.device):
+        rc = lib.sir_layer_norm_act_drop_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(weight), _ptr(bias),
+                                             _ptr(mean), _ptr(rstd), int(act), float(slope), _ptr(dX), _ld(dX, N),
+                                             _ptr(part), _ptr(db_part), 2 * npad, _drop(drop), _stream(X.device))
+    _check(rc, lib)
+    tot = col_sum(part[:parts])
     return tot[:N], tot[npad:npad + N]
 
 

@@ -16,7 +16,15 @@ MI355X modules (tests, ``bench.py --workload``):
   ``Sequential`` sigma lives inside the conv).
 
 ``norm_cls`` (e.g. GraphNorm, ``models/norm.py:7-29``) is called as ``norm(graph, feats)``.
+
+``dropout`` is the layer's ``nn.Dropout`` of the node-level models, at the reference's position: after the
+activation and before the residual add (``ogbn-arxiv/model.py:49,70``), after the activation in zinc order
+(``zinc/model.py:24,56``).  A norm whose ``forward_act`` takes ``dropout`` (this package's three) runs it inside
+its fused pass from a hashed mask that is never stored; otherwise the stack applies ``self.dropout`` itself.
 """
+import functools
+import inspect
+
 from torch import nn
 
 
@@ -27,6 +35,16 @@ def _resid_act(y, resid, activation, order, r_link=None, out_link=None):
         return None
     from .resact import resid_act
     return resid_act(y, resid, activation, order, r_link, out_link)
+
+
+@functools.lru_cache(maxsize=None)
+def _takes_dropout(fn):
+    """True when the ``forward_act`` function ``fn`` has a ``dropout`` parameter."""
+    try:
+        params = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    return "dropout" in params or any(q.kind is inspect.Parameter.VAR_KEYWORD for q in params.values())
 
 
 def _new_link():
@@ -42,7 +60,7 @@ class SIRStack(nn.Module):
     link_residual_grads = True
 
     def __init__(self, conv_cls, hidden, num_layers, activation, agg_type="sum", order="arxiv",
-                 norm_cls=None, conv_activation=None, feat_dropout=0):
+                 norm_cls=None, conv_activation=None, feat_dropout=0, dropout=0):
         super().__init__()
         if order not in ("arxiv", "zinc", "plain"):
             raise ValueError(order)
@@ -54,17 +72,28 @@ class SIRStack(nn.Module):
         self.convs = nn.ModuleList([conv_cls(hidden, hidden, hidden, sigma, feat_dropout, agg_type=agg_type)
                                     for _ in range(num_layers)])
         self.norms = nn.ModuleList([norm_cls(hidden) for _ in range(num_layers)]) if norm_cls else None
+        # the layer dropout (the reference's attribute); fused into the norm pass when the norm offers it
+        self.dropout = nn.Dropout(dropout)
+        self.layer_seeds = None      # the layers' seed words of the last fused-dropout step (one per layer)
 
     def forward(self, graph, feats):
+        p_drop = self.dropout.p if self.training else 0
+        self.layer_seeds = None
         if self.training and getattr(feats, "is_cuda", False):
             # the dropout seeds of every layer in ONE device draw (sirgcn SIRConv's step_seed): one
             # RNG launch per step instead of one per layer (small batches are launch-bound)
             drawing = [c for c in self.convs if hasattr(c, "step_seed") and c.dropout.p > 0]
-            if drawing:
+            # ... and one more word per layer for its fused layer dropout.  A layer's word is never a conv's:
+            # the conv's Q dropout hashes the same (row, col) domain, so the convs' words stay below 2^62
+            # and the layers' get bit 62 set.
+            n_layer = len(self.convs) if p_drop > 0 and self.norms is not None and self.order != "plain" else 0
+            if drawing or n_layer:
                 import torch
-                seeds = torch.randint(0, 2 ** 62, (len(drawing),), device=feats.device, dtype=torch.int64)
+                seeds = torch.randint(0, 2 ** 62, (len(drawing) + n_layer,), device=feats.device, dtype=torch.int64)
                 for j, c in enumerate(drawing):
                     c.step_seed = seeds[j:j + 1]
+                if n_layer:
+                    self.layer_seeds = seeds[len(drawing):].bitwise_or_(1 << 62)
         link = None          # the GradLink of feats when a fused residual pass produced it
         for i, conv in enumerate(self.convs):
             if self.order == "plain":
@@ -72,7 +101,7 @@ class SIRStack(nn.Module):
                 continue
             resid = feats
             feats = conv(graph, feats)
-            if self.norms is None:
+            if self.norms is None and not p_drop > 0:
                 # + resid and the activation in one pass when the operands allow (sirgcn.resact);
                 # the residual gradient of each layer's input handed to the layer that produced it
                 # (resact.GradLink) instead of an autograd add
@@ -89,12 +118,20 @@ class SIRStack(nn.Module):
                 # norm -> act (-> + resid) as one op when the norm offers it (sirgcn.GraphNorm:
                 # one kernel per direction; None: not for this activation / these operands)
                 fuse = getattr(self.norms[i], "forward_act", None)
-                out = fuse(graph, feats, self.activation, resid if self.order == "arxiv" else None) if fuse else None
+                r = resid if self.order == "arxiv" else None
+                if not p_drop > 0:
+                    out = fuse(graph, feats, self.activation, r) if fuse else None
+                elif fuse and self.layer_seeds is not None and _takes_dropout(getattr(fuse, "__func__", fuse)):
+                    out = fuse(graph, feats, self.activation, r, dropout=(self.layer_seeds[i:i + 1], p_drop))
+                else:
+                    out = None          # no fused dropout: norm, activation, self.dropout and the add below
                 if out is not None:
                     feats = out
                     continue
                 feats = self.norms[i](graph, feats)
             feats = self.activation(feats)
+            if p_drop > 0:
+                feats = self.dropout(feats)
             if self.order == "arxiv":
                 feats = feats + resid
         return feats

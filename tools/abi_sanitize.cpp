@@ -4,6 +4,7 @@
 // built kernel objects; needs no GPU: every call below must be rejected (or be a no-op on empty
 // work) before anything is launched.  Exit status 0 = every expectation held and the sanitizers
 // reported nothing.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -166,6 +167,33 @@ int main() {
     }
     expect("pool_work_floats: range", (int)sir_graph_pool_work_floats(8, 2, 65537, SIR_POOL_SUM), -1);
     expect("pool_work_floats: one slab", (int)sir_graph_pool_work_floats(SIR_POOL_SLAB_ROWS, 2, 8, SIR_POOL_MAX), 0);
+    // layer dropout fused into the norms
+    const double* dd = reinterpret_cast<const double*>(buf.data());
+    const double nan = std::nan("");
+    const sir_dropout_t drop_ok = {5, 0.2, nullptr}, drop_nan = {5, nan, nullptr};
+    expect("bn_drop_fwd: NaN p", sir_batch_norm_act_drop_fwd(f, 8, 4, 8, dd, dd, f, f, 2, 0.2f, nullptr, 0, f, 8, &drop_nan,
+                                                             nullptr), SIR_EINVAL, "sir_batch_norm_act_drop_fwd: dropout p is NaN");
+    expect("bn_drop_bwd: NaN p", sir_batch_norm_act_drop_bwd(f, 8, f, 8, 4, 8, dd, dd, f, f, 2, 0.2f, 1, f, 8, f, f, f, &drop_nan,
+                                                             nullptr), SIR_EINVAL, "sir_batch_norm_act_drop_bwd: dropout p is NaN");
+    expect("ln_drop_fwd: NaN p", sir_layer_norm_act_drop_fwd(f, 8, 4, 8, f, f, 1e-5f, 2, 0.2f, nullptr, 0, f, 8, f, f, &drop_nan,
+                                                             nullptr), SIR_EINVAL, "sir_layer_norm_act_drop_fwd: dropout p is NaN");
+    expect("ln_drop_bwd: NaN p", sir_layer_norm_act_drop_bwd(f, 8, f, 8, 4, 8, f, f, f, f, 2, 0.2f, f, 8, f, f, 8, &drop_nan,
+                                                             nullptr), SIR_EINVAL, "sir_layer_norm_act_drop_bwd: dropout p is NaN");
+    expect("gn_drop_fwd: NaN p", sir_graph_norm_act_drop_fwd(off, 2, 8, f, 8, f, f, f, 1e-5f, 2, 0.2f, nullptr, 0, f, 8, f, f,
+                                                             &drop_nan, nullptr), SIR_EINVAL, "sir_graph_norm_act_drop_fwd: dropout p is NaN");
+    expect("gn_drop_bwd: NaN p", sir_graph_norm_act_drop_bwd(off, 2, 8, f, 8, f, 8, f, f, f, f, f, 2, 0.2f, f, 8, f, f, f,
+                                                             &drop_nan, nullptr), SIR_EINVAL, "sir_graph_norm_act_drop_bwd: dropout p is NaN");
+    expect("bn_drop_fwd: ld < N", sir_batch_norm_act_drop_fwd(f, 7, 4, 8, dd, dd, f, f, 2, 0.2f, nullptr, 0, f, 8, &drop_ok, nullptr),
+           SIR_EINVAL, "sir_batch_norm_act_drop_fwd: leading");
+    expect("ln_drop_fwd: N out of range", sir_layer_norm_act_drop_fwd(f, 4096, 4, 1025, f, f, 1e-5f, 2, 0.2f, nullptr, 0, f, 4096, f,
+                                                                      f, &drop_ok, nullptr), SIR_EINVAL, "N must be in [1, 1024]");
+    expect("gn_drop_bwd: NULL dX", sir_graph_norm_act_drop_bwd(off, 2, 8, f, 8, f, 8, f, f, f, f, f, 2, 0.2f, nullptr, 8, f, f, f,
+                                                               &drop_ok, nullptr), SIR_EINVAL, "NULL");
+    expect("bn_drop_fwd: empty work is a no-op", sir_batch_norm_act_drop_fwd(nullptr, 8, 0, 8, nullptr, nullptr, nullptr, nullptr, 2,
+                                                                            0.2f, nullptr, 0, nullptr, 8, &drop_ok, nullptr), SIR_OK);
+    expect("gn_drop_fwd: no graphs is a no-op", sir_graph_norm_act_drop_fwd(nullptr, 0, 8, nullptr, 8, nullptr, nullptr, nullptr, 1e-5f,
+                                                                           2, 0.2f, nullptr, 0, nullptr, 8, nullptr, nullptr, &drop_ok,
+                                                                           nullptr), SIR_OK);
     std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "ok", failures);
     return failures ? 1 : 0;
 }

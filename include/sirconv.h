@@ -27,6 +27,7 @@
  *    into all three: sir_{batch,layer,graph}_norm_act_drop_fwd / _bwd;
  *  - the graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling, dgl.broadcast_nodes; ogbg-molhiv/model.py:69,85,
  *    zinc/model.py:41): sir_graph_pool_fwd / _bwd (sir_graph_pool_work_floats, sir_graph_pool_slab_rows);
+ *  - Correct & Smooth's label propagation (ogbn-arxiv/correct_and_smooth.py:41-58): sir_label_prop_step;
  *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm.
  *
  * Conventions
@@ -54,7 +55,7 @@
  *    selection, never by a multiply.
  *    Propagation: an Inf or NaN the result does depend on is never turned into a finite number.  The
  *    kernels that select, add and scale by a finite factor (edge passes, edge-feature kernels, the
- *    edge-materialised helpers, resid-act, readout sum / mean, column sums) return the class IEEE
+ *    edge-materialised helpers, resid-act, readout sum / mean, column sums, sir_label_prop_step) return the class IEEE
  *    arithmetic gives (NaN, +Inf, -Inf; ReLU(-Inf) = 0, LeakyReLU(-Inf) = -Inf, Inf - Inf = NaN).
  *    Maximum (sir_segment_max, the edge-MLP max forward in every form, sir_graph_pool_fwd max):
  *    torch.max's order — a NaN beats every number — with the first of equal candidates, and the first
@@ -663,6 +664,41 @@ int sir_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int 
                        const void* X, int64_t ldx, void* P, int64_t ldp, int32_t* arg, float* work, void* stream);
 int sir_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int op, int dtype,
                        const void* dP, int64_t ldg, const int32_t* arg, void* dX, int64_t lddx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Correct & Smooth label propagation (ogbn-arxiv/correct_and_smooth.py:41-58, `label_spreading`): one step
+ *     graph.ndata['y'] = y * norm; update_all(copy_u('y', 'm'), sum | mean); y = ndata['y'] * norm
+ *     y = alpha * y + (1 - alpha) * y0; y = post_step(y)
+ * in one launch over the destination CSR (rows = destinations, col = sources, the plan's items / splits).
+ * Added under ABI 17 (a new symbol only).  fp32, V rows of F columns.  For row v, in-edges in CSR order:
+ *   s[v]   = sum_e (SYM ? Y[u] * norm[u] : Y[u])      each product rounded, added in edge order from 0
+ *   p[v]   = SYM ? s[v] * norm[v] : MEAN ? s[v] / (float)max(deg v, 1) : s[v]      (IEEE division)
+ *   out[v] = alpha * p[v] + beta * Y0[v]              two rounded products and one add, never an FMA
+ *   post   : SIR_LP_POST_NONE | _CLAMP: torch.clamp(out, lo, hi), a NaN stays NaN
+ *            | _FIX: out[v] = Yfix[v] where fixed[v] != 0 (uint8 [V]); such a row is not gathered at all.
+ * agg = SIR_AGG_SUM / _MEAN / _SYM.  SYM: `norm` [V] is the IN-degree normaliser deg_in^-1/2 on both sides
+ * (correct_and_smooth.py:44-51 takes in_degrees() for the source factor too): sir_degree_norms' in_norm.
+ * beta is its own argument: the caller passes (float)(1.0 - alpha) with the subtraction in double, as torch
+ * forms (1 - alpha) * y0.
+ * Exactness: a row of one work item (at most the plan's chunk of edges) is the reference's CPU result bit for
+ * bit.  A split row's items leave their partial sums in `partial` (n_slots * F floats) and a second launch
+ * adds them in slot order and runs the same epilogue: deterministic, not bit-equal to the one-pass sum.
+ * Any 1 <= F <= 65536 and any leading dimension >= F: float4 accesses when F % 4 == 0, every leading
+ * dimension is a multiple of 4 and every matrix is 16-B aligned, single floats otherwise.  No atomics, no
+ * host synchronisation (graph-capturable); run to run bit-identical.
+ * out must not be Y (rows are gathered across the matrix while out is written); Y0, Yfix and Y may alias
+ * each other, and out may be Y0 or Yfix.  V == 0: no-op.  col may be NULL when the graph has no edges.
+ * Non-finite values: a NaN or Inf in Y[u] reaches every out-neighbour of u (and nothing else in that step);
+ * nothing at or beyond column F of a padded row is read or written, so pad columns may hold anything and
+ * out's keep their bits; a fixed row takes Yfix whatever Y, Y0 and `partial` hold.
+ * ------------------------------------------------------------------------------------------- */
+enum { SIR_LP_POST_NONE = 0, SIR_LP_POST_CLAMP = 1, SIR_LP_POST_FIX = 2 };
+int sir_label_prop_step(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
+                        const int32_t* splits, int64_t n_splits, int64_t V, int64_t F,
+                        const float* Y, int64_t ldy, const float* Y0, int64_t ldy0,
+                        const float* norm, int agg, float alpha, float beta,
+                        int post, float lo, float hi, const uint8_t* fixed, const float* Yfix, int64_t ldf,
+                        float* out, int64_t ldo, float* partial, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Device-side graph plan build.  Replaces DGL's lazily built in-edge CSC

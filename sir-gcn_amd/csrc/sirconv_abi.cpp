@@ -1141,6 +1141,40 @@ int sir_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int 
                                               static_cast<hipStream_t>(stream)), "too many slab slots for one launch");
 }
 
+// ------------------------------------------------------------------------------ C&S label propagation
+int sir_label_prop_step(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
+                        const int32_t* splits, int64_t n_splits, int64_t V, int64_t F,
+                        const float* Y, int64_t ldy, const float* Y0, int64_t ldy0,
+                        const float* norm, int agg, float alpha, float beta,
+                        int post, float lo, float hi, const uint8_t* fixed, const float* Yfix, int64_t ldf,
+                        float* out, int64_t ldo, float* partial, void* stream) {
+    const char* fn = "sir_label_prop_step";
+    if (F <= 0 || F > 65536) return fail(SIR_EINVAL, fn, "F must be in [1, 65536]");
+    if (V < 0 || V >= INT32_MAX) return fail(SIR_EINVAL, fn, "V must be in [0, 2^31 - 1)");
+    if (n_items < 0 || n_splits < 0) return fail(SIR_EINVAL, fn, "negative item/split count");
+    if (agg != SIR_AGG_SUM && agg != SIR_AGG_MEAN && agg != SIR_AGG_SYM)
+        return fail(SIR_EINVAL, fn, "agg must be SUM, MEAN or SYM");
+    if (post != SIR_LP_POST_NONE && post != SIR_LP_POST_CLAMP && post != SIR_LP_POST_FIX)
+        return fail(SIR_EINVAL, fn, "post must be SIR_LP_POST_NONE, _CLAMP or _FIX");
+    if (ldy < F || ldy0 < F || ldo < F || (post == SIR_LP_POST_FIX && ldf < F))
+        return fail(SIR_EINVAL, fn, "leading dimensions must be >= F");
+    if (V == 0) return SIR_OK;
+    if (Y == nullptr || Y0 == nullptr || out == nullptr) return fail(SIR_EINVAL, fn, "NULL Y / Y0 / out");
+    if (out == Y) return fail(SIR_EINVAL, fn, "out must not alias Y (rows are gathered across the matrix)");
+    if (agg == SIR_AGG_SYM && norm == nullptr) return fail(SIR_EINVAL, fn, "SYM needs norm");
+    if (post == SIR_LP_POST_FIX && (fixed == nullptr || Yfix == nullptr))
+        return fail(SIR_EINVAL, fn, "FIX needs fixed and Yfix");
+    if (n_items > 0 && items == nullptr) return fail(SIR_EINVAL, fn, "NULL items");
+    if (n_splits > 0 && (splits == nullptr || partial == nullptr))
+        return fail(SIR_EINVAL, fn, "split rows need `splits` and a `partial` workspace");
+    sir::LabelPropArgs a{};
+    a.rowptr = rowptr; a.col = col; a.items = items; a.n_items = n_items; a.splits = splits; a.n_splits = n_splits;
+    a.V = V; a.F = (int)F; a.Y = Y; a.ldy = ldy; a.Y0 = Y0; a.ldy0 = ldy0; a.norm = norm; a.agg = agg;
+    a.alpha = alpha; a.beta = beta; a.post = post; a.lo = lo; a.hi = hi; a.fixed = fixed; a.Yfix = Yfix; a.ldf = ldf;
+    a.out = out; a.ldo = ldo; a.partial = partial;
+    return finish(fn, sir::run_label_prop(a, static_cast<hipStream_t>(stream)), "too many work items for one launch");
+}
+
 int64_t sir_csr_build_workspace(int64_t n_rows, int64_t E) {
     if (n_rows < 0 || E < 0 || E >= INT32_MAX || n_rows >= INT32_MAX) return -1;
     return sir::csr_build_workspace(n_rows, E);

@@ -148,6 +148,30 @@ hipError_t run_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int F, i
 hipError_t run_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int F, int op, int dtype, const void* dP,
                               int64_t ldg, const int* arg, void* dX, int64_t lddx, hipStream_t st);
 
+// one label-spreading step of Correct & Smooth (sirconv_labelprop.hip); the fields are sir_label_prop_step's
+struct LabelPropArgs {
+    const int* rowptr;
+    const int* col;
+    const int32_t* items;
+    int64_t n_items;
+    const int32_t* splits;
+    int64_t n_splits;
+    int64_t V;
+    int F;
+    const float* Y;  int64_t ldy;
+    const float* Y0; int64_t ldy0;
+    const float* norm;
+    int agg;
+    float alpha, beta;
+    int post;
+    float lo, hi;
+    const uint8_t* fixed;
+    const float* Yfix; int64_t ldf;
+    float* out;  int64_t ldo;
+    float* partial;
+};
+hipError_t run_label_prop(const LabelPropArgs& a, hipStream_t st);
+
 hipError_t run_degree_norms(const int* rowptr_a, float* norm_a, const int* rowptr_b, float* norm_b,
                             int64_t n, hipStream_t st);
 

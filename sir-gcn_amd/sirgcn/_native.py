@@ -66,6 +66,8 @@ SIGNATURES = {
     "sir_graph_pool_work_floats": (ctypes.c_int64, [_I64, _I64, _I64, _I]),
     "sir_graph_pool_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _I64, _P, _P, _P]),
     "sir_graph_pool_bwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _P, _I64, _P]),
+    "sir_label_prop_step": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I, _F, _F,
+                                           _I, _F, _F, _P, _P, _I64, _P, _I64, _P, _P]),
     "sir_edge_gather_add": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "sir_edge_gather_act": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _F, _P, _I64, _P, _P]),
     "sir_segment_sum": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _I, _P, _I64,
@@ -1024,3 +1026,37 @@ def max_dw_qk(dcsr, arg, dY, Q, K, O, act1, slope):
     _check(rc, lib)
     tot = col_sum(wpart)
     return tot[:O * H].view(O, H), tot[O * H:O * H + O]
+
+
+# ------------------------------------------------------------------------------ C&S label propagation
+LP_POST_NONE, LP_POST_CLAMP, LP_POST_FIX = 0, 1, 2      # SIR_LP_POST_*
+
+
+def label_prop_step(csr, Y, Y0, norm, agg, alpha, beta, out, post=LP_POST_NONE, lo=0.0, hi=0.0, fixed=None,
+                    Yfix=None, partial=None):
+    """One label-spreading step over the destination CSR (``sir_label_prop_step``): out = post(alpha *
+    agg(Y) + beta * Y0), fp32 [V, F] with unit-stride rows.  ``norm``: the in-degree normaliser (SYM);
+    ``fixed`` uint8 [V] and ``Yfix`` for LP_POST_FIX; ``partial``: n_slots * F floats when the plan has
+    split rows."""
+    lib = _lib if _lib is not None else load()
+    V, F = out.shape
+    dev = out.device
+    for t in (Y, Y0, out) + ((Yfix,) if Yfix is not None else ()):
+        if t.dtype is not torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != V:
+            raise RuntimeError("label_prop_step: fp32 [V, F] matrices with unit-stride rows")
+    if fixed is not None and not (fixed.dtype is torch.uint8 and fixed.is_contiguous() and fixed.numel() == V):
+        raise RuntimeError("label_prop_step: fixed must be a contiguous uint8 [V] tensor")
+    args = (csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.col.numel() else None, csr.items.data_ptr(), csr.n_items,
+            None if csr.splits is None else csr.splits.data_ptr(), csr.n_splits, V, F,
+            Y.data_ptr(), Y.stride(0), Y0.data_ptr(), Y0.stride(0), None if norm is None else norm.data_ptr(),
+            AGG[agg], float(alpha), float(beta), int(post), float(lo), float(hi),
+            None if fixed is None else fixed.data_ptr(), None if Yfix is None else Yfix.data_ptr(),
+            0 if Yfix is None else Yfix.stride(0), out.data_ptr(), out.stride(0),
+            None if partial is None else partial.data_ptr(), _stream_of(dev))
+    if _timing is None:
+        rc = lib.sir_label_prop_step(*args)
+    else:
+        with _Timed("sir_label_prop_step", dev):
+            rc = lib.sir_label_prop_step(*args)
+    if rc != 0:
+        _check(rc, lib)

@@ -167,6 +167,41 @@ int main() {
     }
     expect("pool_work_floats: range", (int)sir_graph_pool_work_floats(8, 2, 65537, SIR_POOL_SUM), -1);
     expect("pool_work_floats: one slab", (int)sir_graph_pool_work_floats(SIR_POOL_SLAB_ROWS, 2, 8, SIR_POOL_MAX), 0);
+    // C&S label propagation: f / f2 / f3 stand for Y / Y0 / out (out must differ from Y)
+    {
+        float* f2 = f + 16;
+        float* f3 = f + 32;
+        const uint8_t* u8 = reinterpret_cast<const uint8_t*>(buf.data());
+        auto lp = [&](int64_t V, int64_t F, const float* Y, int64_t ldy, const float* Y0, const float* norm, int agg, int post,
+                      const uint8_t* fixed, const float* Yfix, int64_t ldf, float* out, int64_t ldo, int64_t n_splits,
+                      float* partial) {
+            return sir_label_prop_step(p, p, p, 8, n_splits ? p : nullptr, n_splits, V, F, Y, ldy, Y0, 8, norm, agg, 0.8f, 0.2f,
+                                       post, 0.f, 1.f, fixed, Yfix, ldf, out, ldo, partial, nullptr);
+        };
+        const int S = SIR_AGG_SYM, N0 = SIR_LP_POST_NONE, FX = SIR_LP_POST_FIX;
+        expect("label_prop: F out of range", lp(8, 65537, f, 1 << 17, f2, f, S, N0, nullptr, nullptr, 0, f3, 1 << 17, 0, nullptr),
+               SIR_EINVAL, "sir_label_prop_step: F must be");
+        expect("label_prop: negative V", lp(-1, 8, f, 8, f2, f, S, N0, nullptr, nullptr, 0, f3, 8, 0, nullptr), SIR_EINVAL,
+               "sir_label_prop_step: V must be");
+        expect("label_prop: ld < F", lp(8, 8, f, 7, f2, f, S, N0, nullptr, nullptr, 0, f3, 8, 0, nullptr), SIR_EINVAL, "leading");
+        expect("label_prop: ldf < F", lp(8, 8, f, 8, f2, f, S, FX, u8, f2, 7, f3, 8, 0, nullptr), SIR_EINVAL, "leading");
+        expect("label_prop: bad agg", lp(8, 8, f, 8, f2, f, 3, N0, nullptr, nullptr, 0, f3, 8, 0, nullptr), SIR_EINVAL, "agg must be");
+        expect("label_prop: SYM needs norm", lp(8, 8, f, 8, f2, nullptr, S, N0, nullptr, nullptr, 0, f3, 8, 0, nullptr), SIR_EINVAL,
+               "SYM needs norm");
+        expect("label_prop: bad post", lp(8, 8, f, 8, f2, f, S, 3, nullptr, nullptr, 0, f3, 8, 0, nullptr), SIR_EINVAL, "post must be");
+        expect("label_prop: FIX needs fixed", lp(8, 8, f, 8, f2, f, S, FX, nullptr, f2, 8, f3, 8, 0, nullptr), SIR_EINVAL, "FIX needs");
+        expect("label_prop: FIX needs Yfix", lp(8, 8, f, 8, f2, f, S, FX, u8, nullptr, 8, f3, 8, 0, nullptr), SIR_EINVAL, "FIX needs");
+        expect("label_prop: NULL Y", lp(8, 8, nullptr, 8, f2, f, S, N0, nullptr, nullptr, 0, f3, 8, 0, nullptr), SIR_EINVAL, "NULL");
+        expect("label_prop: NULL out", lp(8, 8, f, 8, f2, f, S, N0, nullptr, nullptr, 0, nullptr, 8, 0, nullptr), SIR_EINVAL, "NULL");
+        expect("label_prop: partial needed", lp(8, 8, f, 8, f2, f, S, N0, nullptr, nullptr, 0, f3, 8, 1, nullptr), SIR_EINVAL,
+               "split rows need");
+        expect("label_prop: out == Y", lp(8, 8, f, 8, f2, f, S, N0, nullptr, nullptr, 0, f, 8, 0, nullptr), SIR_EINVAL,
+               "sir_label_prop_step: out must not alias Y");
+        for (int agg = 0; agg < 3; ++agg)
+            expect("label_prop: no rows is a no-op", sir_label_prop_step(nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 40, nullptr, 40,
+                                                                        nullptr, 40, nullptr, agg, 0.8f, 0.2f, N0, 0.f, 1.f, nullptr,
+                                                                        nullptr, 0, nullptr, 40, nullptr, nullptr), SIR_OK);
+    }
     // layer dropout fused into the norms
     const double* dd = reinterpret_cast<const double*>(buf.data());
     const double nan = std::nan("");

@@ -82,9 +82,9 @@ int graph_norm_act_fwd(const char* fn, const int64_t* off, int64_t B, int64_t F,
     if (B > 0 && (off == nullptr || X == nullptr || weight == nullptr || Y == nullptr || mean == nullptr ||
                   std_ == nullptr))
         return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_graph_norm_drop_fwd(off, B, (int)F, X, ldx, weight, bias, mean_scale, eps, act, slope, R,
-                                                   ldr, Y, ldy, mean, std_, to_drop(drop, 0),
-                                                   static_cast<hipStream_t>(stream)), nullptr);
+    return finish(fn, sir::run_graph_norm_fwd(off, B, (int)F, X, ldx, weight, bias, mean_scale, eps, act, slope, R,
+                                              ldr, Y, ldy, mean, std_, to_drop(drop, 0),
+                                              static_cast<hipStream_t>(stream)), nullptr);
 }
 
 int graph_norm_act_bwd(const char* fn, const int64_t* off, int64_t B, int64_t F, const float* X, int64_t ldx,
@@ -100,9 +100,9 @@ int graph_norm_act_bwd(const char* fn, const int64_t* off, int64_t B, int64_t F,
                   std_ == nullptr || dX == nullptr || dw_part == nullptr || db_part == nullptr))
         return fail(SIR_EINVAL, fn, "NULL buffer");
     if (mean_scale != nullptr && dms_part == nullptr && B > 0) return fail(SIR_EINVAL, fn, "dms_part needed");
-    return finish(fn, sir::run_graph_norm_drop_bwd(off, B, (int)F, X, ldx, dY, ldg, weight, bias, mean_scale, mean, std_,
-                                                   act, slope, dX, lddx, dw_part, dms_part, db_part, to_drop(drop, 0),
-                                                   static_cast<hipStream_t>(stream)), nullptr);
+    return finish(fn, sir::run_graph_norm_bwd(off, B, (int)F, X, ldx, dY, ldg, weight, bias, mean_scale, mean, std_,
+                                              act, slope, dX, lddx, dw_part, dms_part, db_part, to_drop(drop, 0),
+                                              static_cast<hipStream_t>(stream)), nullptr);
 }
 
 int check_nodenorm(const char* fn, int64_t M, int64_t N, int64_t n_max, int act) {
@@ -123,8 +123,8 @@ int batch_norm_act_fwd(const char* fn, const float* X, int64_t ldx, int64_t M, i
     if (M == 0) return SIR_OK;
     if (X == nullptr || mean == nullptr || invstd == nullptr || weight == nullptr || bias == nullptr || Y == nullptr)
         return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_batch_norm_act_drop_fwd(X, ldx, M, (int)N, mean, invstd, weight, bias, act, slope, R, ldr,
-                                                       Y, ldy, to_drop(drop, 0), static_cast<hipStream_t>(stream)),
+    return finish(fn, sir::run_batch_norm_act_fwd(X, ldx, M, (int)N, mean, invstd, weight, bias, act, slope, R, ldr,
+                                                  Y, ldy, to_drop(drop, 0), static_cast<hipStream_t>(stream)),
                   nullptr);
 }
 
@@ -141,9 +141,9 @@ int batch_norm_act_bwd(const char* fn, const float* X, int64_t ldx, const float*
         dX == nullptr || dweight == nullptr || dbias == nullptr || work == nullptr)
         return fail(SIR_EINVAL, fn, "NULL buffer");
     if ((reinterpret_cast<uintptr_t>(work) & 7u) != 0) return fail(SIR_EINVAL, fn, "work must be 8-B aligned");
-    return finish(fn, sir::run_batch_norm_act_drop_bwd(X, ldx, dY, ldg, M, (int)N, mean, invstd, weight, bias, act, slope,
-                                                       training, dX, lddx, dweight, dbias, work, to_drop(drop, 0),
-                                                       static_cast<hipStream_t>(stream)), nullptr);
+    return finish(fn, sir::run_batch_norm_act_bwd(X, ldx, dY, ldg, M, (int)N, mean, invstd, weight, bias, act, slope,
+                                                  training, dX, lddx, dweight, dbias, work, to_drop(drop, 0),
+                                                  static_cast<hipStream_t>(stream)), nullptr);
 }
 
 int layer_norm_act_fwd(const char* fn, const float* X, int64_t ldx, int64_t M, int64_t N, const float* weight,
@@ -156,8 +156,8 @@ int layer_norm_act_fwd(const char* fn, const float* X, int64_t ldx, int64_t M, i
     if (M == 0) return SIR_OK;
     if (X == nullptr || weight == nullptr || bias == nullptr || Y == nullptr || mean == nullptr || rstd == nullptr)
         return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_layer_norm_act_drop_fwd(X, ldx, M, (int)N, weight, bias, eps, act, slope, R, ldr, Y, ldy,
-                                                       mean, rstd, to_drop(drop, 0), static_cast<hipStream_t>(stream)),
+    return finish(fn, sir::run_layer_norm_act_fwd(X, ldx, M, (int)N, weight, bias, eps, act, slope, R, ldr, Y, ldy,
+                                                  mean, rstd, to_drop(drop, 0), static_cast<hipStream_t>(stream)),
                   nullptr);
 }
 
@@ -173,9 +173,9 @@ int layer_norm_act_bwd(const char* fn, const float* X, int64_t ldx, const float*
     if (X == nullptr || dY == nullptr || weight == nullptr || bias == nullptr || mean == nullptr || rstd == nullptr ||
         dX == nullptr || dw_part == nullptr || db_part == nullptr)
         return fail(SIR_EINVAL, fn, "NULL buffer");
-    return finish(fn, sir::run_layer_norm_act_drop_bwd(X, ldx, dY, ldg, M, (int)N, weight, bias, mean, rstd, act, slope,
-                                                       dX, lddx, dw_part, db_part, ldp, to_drop(drop, 0),
-                                                       static_cast<hipStream_t>(stream)), nullptr);
+    return finish(fn, sir::run_layer_norm_act_bwd(X, ldx, dY, ldg, M, (int)N, weight, bias, mean, rstd, act, slope,
+                                                  dX, lddx, dw_part, db_part, ldp, to_drop(drop, 0),
+                                                  static_cast<hipStream_t>(stream)), nullptr);
 }
 
 }  // namespace
@@ -906,8 +906,8 @@ int sir_graph_norm_fwd(const int64_t* off, int64_t B, int64_t F, const float* X,
                   std_ == nullptr))
         return fail(SIR_EINVAL, fn, "NULL buffer");
     return finish(fn, sir::run_graph_norm_fwd(off, B, (int)F, X, ldx, weight, bias, mean_scale, eps, SIR_ACT_IDENTITY,
-                                              0.f, nullptr, 0, Y, ldy, mean, std_, static_cast<hipStream_t>(stream)),
-                  nullptr);
+                                              0.f, nullptr, 0, Y, ldy, mean, std_, sir::Drop(),
+                                              static_cast<hipStream_t>(stream)), nullptr);
 }
 
 
@@ -981,7 +981,7 @@ int sir_graph_norm_bwd(const int64_t* off, int64_t B, int64_t F, const float* X,
         return fail(SIR_EINVAL, fn, "NULL buffer");
     if (mean_scale != nullptr && dms_part == nullptr && B > 0) return fail(SIR_EINVAL, fn, "dms_part needed");
     return finish(fn, sir::run_graph_norm_bwd(off, B, (int)F, X, ldx, dY, ldg, weight, nullptr, mean_scale, mean, std_,
-                                              SIR_ACT_IDENTITY, 0.f, dX, lddx, dw_part, dms_part, db_part,
+                                              SIR_ACT_IDENTITY, 0.f, dX, lddx, dw_part, dms_part, db_part, sir::Drop(),
                                               static_cast<hipStream_t>(stream)), nullptr);
 }
 

@@ -24,23 +24,6 @@
 namespace sir {
 namespace {
 
-template <int VW>
-__device__ __forceinline__ void gld(float (&d)[VW], const float* __restrict__ p) {
-    if constexpr (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-        d[0] = p[0];
-    }
-}
-
-template <int VW>
-__device__ __forceinline__ void gst(float* __restrict__ p, const float (&s)[VW]) {
-    if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]);
-    else p[0] = s[0];
-}
-
-
 // Walk rows [r0, r1) in node order, RB rows' loads in flight at a time (a molecule has ~25 rows: the
 // forward's passes take one memory latency each, the backward's two; a one-load-per-iteration loop
 // paid one latency per row and pass, ~40 us per launch on cfg5);
@@ -52,7 +35,7 @@ __device__ __forceinline__ void walk_rows(int64_t r0, int64_t r1, const float* _
     for (; i + RB <= r1; i += RB) {
         float v[RB][VW];
 #pragma unroll
-        for (int k = 0; k < RB; ++k) gld<VW>(v[k], base + (i + k) * ld + c * VW);
+        for (int k = 0; k < RB; ++k) vld<VW>(v[k], base + (i + k) * ld + c * VW);
 #pragma unroll
         for (int k = 0; k < RB; ++k) f(i + k, v[k]);
     }
@@ -60,7 +43,7 @@ __device__ __forceinline__ void walk_rows(int64_t r0, int64_t r1, const float* _
         const int n = (int)(r1 - i);
         float v[RB][VW];
 #pragma unroll
-        for (int k = 0; k < RB; ++k) gld<VW>(v[k], base + (i + (k < n ? k : 0)) * ld + c * VW);
+        for (int k = 0; k < RB; ++k) vld<VW>(v[k], base + (i + (k < n ? k : 0)) * ld + c * VW);
 #pragma unroll
         for (int k = 0; k < RB; ++k)
             if (k < n) f(i + k, v[k]);
@@ -75,8 +58,8 @@ __device__ __forceinline__ void walk_rows2(int64_t r0, int64_t r1, const float* 
         float u[RB][VW], v[RB][VW];
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
-            gld<VW>(u[k], a + (i + k) * lda + c * VW);
-            gld<VW>(v[k], b + (i + k) * ldb + c * VW);
+            vld<VW>(u[k], a + (i + k) * lda + c * VW);
+            vld<VW>(v[k], b + (i + k) * ldb + c * VW);
         }
 #pragma unroll
         for (int k = 0; k < RB; ++k) f(i + k, u[k], v[k]);
@@ -87,28 +70,13 @@ __device__ __forceinline__ void walk_rows2(int64_t r0, int64_t r1, const float* 
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
             const int64_t q = i + (k < n ? k : 0);
-            gld<VW>(u[k], a + q * lda + c * VW);
-            gld<VW>(v[k], b + q * ldb + c * VW);
+            vld<VW>(u[k], a + q * lda + c * VW);
+            vld<VW>(v[k], b + q * ldb + c * VW);
         }
 #pragma unroll
         for (int k = 0; k < RB; ++k)
             if (k < n) f(i + k, u[k], v[k]);
     }
-}
-
-// the stack's activation after the norm (ogbn-arxiv/model.py:65-73: h = act(norm(h)) + resid), the
-// ops of torch's relu / leaky_relu and their backward (x > 0 ? g : 0 / g * slope)
-template <int ACT>
-__device__ __forceinline__ float gn_act(float y, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y <= 0.f ? 0.f : y;         // ReLU(NaN) = NaN, as torch.relu
-    else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? y : y * slope;
-    else return y;
-}
-template <int ACT>
-__device__ __forceinline__ float gn_act_bwd(float y, float g, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y > 0.f ? g : 0.f;
-    else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? g : g * slope;
-    else return g;
 }
 
 template <int VW, int ACT, bool DROP>
@@ -133,9 +101,9 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
 #pragma unroll
         for (int x = 0; x < VW; ++x) s[x] += v[x];
     });
-    gld<VW>(wv, w + c * VW);
-    if (bias) gld<VW>(bv, bias + c * VW);
-    if (ms) gld<VW>(mv, ms + c * VW);
+    vld<VW>(wv, w + c * VW);
+    if (bias) vld<VW>(bv, bias + c * VW);
+    if (ms) vld<VW>(mv, ms + c * VW);
 #pragma unroll
     for (int x = 0; x < VW; ++x) {
         s[x] = (r1 > r0) ? s[x] / nf : 0.f;               // norm.py:21 mean
@@ -159,7 +127,7 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
             const float d = v[x] - t[x];
             y[x] = wv[x] * d / sd[x];
             if (bias) y[x] = y[x] + bv[x];
-            y[x] = gn_act<ACT>(y[x], slope);
+            y[x] = norm_act<ACT>(y[x], slope);
             if constexpr (DROP) y[x] = drop_keep(drop, rh, c * VW + x) ? y[x] * drop.scale : 0.f;
         }
     };
@@ -167,7 +135,7 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         walk_rows<VW>(r0, r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
             float y[VW];
             norm_row(i, v, y);
-            gst<VW>(Y + i * ldy + c * VW, y);
+            vst<VW>(Y + i * ldy + c * VW, y);
         });
     } else {                                              // + resid (model.py:73)
         walk_rows2<VW>(r0, r1, X, ldx, R, ldr, c, [&](int64_t i, const float (&v)[VW], const float (&r)[VW]) {
@@ -175,11 +143,11 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
             norm_row(i, v, y);
 #pragma unroll
             for (int x = 0; x < VW; ++x) y[x] = y[x] + r[x];
-            gst<VW>(Y + i * ldy + c * VW, y);
+            vst<VW>(Y + i * ldy + c * VW, y);
         });
     }
-    gst<VW>(mean_out + b * F + c * VW, s);
-    gst<VW>(std_out + b * F + c * VW, sd);
+    vst<VW>(mean_out + b * F + c * VW, s);
+    vst<VW>(std_out + b * F + c * VW, sd);
 }
 
 // ACT: dY is the gradient of act(y); the kernel takes g = act'(y) dY with y = the forward's norm output,
@@ -202,15 +170,15 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
     const int64_t r0 = off[b], r1 = off[b + 1];
     const float nf = (float)(r1 - r0);
     float wv[VW], mv[VW], mu[VW], sd[VW], t[VW], A[VW], G[VW], Bs[VW], bv[VW];
-    gld<VW>(wv, w + c * VW);
-    if (ACT != SIR_ACT_IDENTITY && bias != nullptr) gld<VW>(bv, bias + c * VW);
-    if (ms) gld<VW>(mv, ms + c * VW);
+    vld<VW>(wv, w + c * VW);
+    if (ACT != SIR_ACT_IDENTITY && bias != nullptr) vld<VW>(bv, bias + c * VW);
+    if (ms) vld<VW>(mv, ms + c * VW);
     else {
 #pragma unroll
         for (int x = 0; x < VW; ++x) mv[x] = 1.f;
     }
-    gld<VW>(mu, mean + b * F + c * VW);
-    gld<VW>(sd, sdv + b * F + c * VW);
+    vld<VW>(mu, mean + b * F + c * VW);
+    vld<VW>(sd, sdv + b * F + c * VW);
 #pragma unroll
     for (int x = 0; x < VW; ++x) { t[x] = ms ? mu[x] * mv[x] : mu[x]; A[x] = 0.f; G[x] = 0.f; Bs[x] = 0.f; }
     // act'(y) dY for the row (y: the forward's norm output, same ops)
@@ -226,7 +194,7 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
             } else {
                 float y = wv[x] * (v[x] - t[x]) / sd[x];
                 if (bias) y = y + bv[x];
-                g[x] = gn_act_bwd<ACT>(y, g0, slope);
+                g[x] = norm_act_bwd<ACT>(y, g0, slope);
             }
         }
     };
@@ -254,7 +222,7 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         float o[VW];
 #pragma unroll
         for (int x = 0; x < VW; ++x) o[x] = (k1[x] * g[x] - k2[x] * (v[x] - t[x])) - mv[x] * Bs[x] / nf;
-        gst<VW>(dX + i * lddx + c * VW, o);
+        vst<VW>(dX + i * lddx + c * VW, o);
     });
     float pw[VW], pm[VW];
 #pragma unroll
@@ -262,18 +230,16 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         pw[x] = (r1 > r0) ? A[x] / sd[x] : 0.f;
         pm[x] = -(mu[x] * Bs[x]);
     }
-    gst<VW>(dw_part + b * F + c * VW, pw);
-    if (dms_part) gst<VW>(dms_part + b * F + c * VW, pm);
-    gst<VW>(db_part + b * F + c * VW, G);
+    vst<VW>(dw_part + b * F + c * VW, pw);
+    if (dms_part) vst<VW>(dms_part + b * F + c * VW, pm);
+    vst<VW>(db_part + b * F + c * VW, G);
 }
-
-bool al(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // One column per lane (VW 1) by default: a wave walks its graph's rows in order three times, so
 // its time is its instruction latency over the rows — 16-byte columns (VW 4) give each wave 4x the
 // work and 4x fewer waves: config 5 (64 molecules, F = 300) 10.96 -> 6.48 us forward, 9.66 -> 6.63
 // backward; 10,000 graphs at F = 128: 68.7 -> 54.5 forward, 108 vs 111 backward
-// (tools/dbg/gn_probe.hip, profiles/r05_graphnorm.txt).  env SIR_GN_VW=4 takes the wide kernels.
+// (profiles/r05_graphnorm.txt).  env SIR_GN_VW=4 takes the wide kernels.
 bool gn_wide(int64_t, int) {
     const char* e = getenv("SIR_GN_VW");
     return e != nullptr && atoi(e) == 4;
@@ -281,128 +247,35 @@ bool gn_wide(int64_t, int) {
 
 }  // namespace
 
-
-namespace {
-
-template <int ACT, bool DROP>
-void launch_gn_fwd(bool v4, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int F, int n_cc,
-                   const float* X, int64_t ldx, const float* w, const float* bias, const float* ms, float eps,
-                   float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd,
-                   const Drop& drop) {
-    if (v4)
-        hipLaunchKernelGGL((k_gn_fwd<4, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w, bias, ms,
-                           eps, slope, R, ldr, Y, ldy, mean, sd, drop);
-    else
-        hipLaunchKernelGGL((k_gn_fwd<1, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w, bias, ms,
-                           eps, slope, R, ldr, Y, ldy, mean, sd, drop);
-}
-
-template <bool DROP>
-hipError_t gn_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* w, const float* bias,
-                  const float* ms, float eps, int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
-                  float* mean, float* sd, const Drop& drop, hipStream_t st) {
+hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* w,
+                              const float* bias, const float* ms, float eps, int act, float slope, const float* R,
+                              int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd, const Drop& drop,
+                              hipStream_t st) {
     if (B == 0) return hipSuccess;
     const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
                     al(R) && al(w) && al(bias) && al(ms) && al(mean) && al(sd) && gn_wide(B, F);
-    const int vw = v4 ? 4 : 1;
-    const int n_cc = (F / vw + 63) / 64;
+    const int n_cc = (F / (v4 ? 4 : 1) + 63) / 64;
     const unsigned blocks = (unsigned)(B * n_cc);
-    switch (act) {
-    case SIR_ACT_IDENTITY:
-        launch_gn_fwd<SIR_ACT_IDENTITY, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y,
-                                              ldy, mean, sd, drop);
-        break;
-    case SIR_ACT_RELU:
-        launch_gn_fwd<SIR_ACT_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr, Y, ldy,
-                                          mean, sd, drop);
-        break;
-    case SIR_ACT_LEAKY_RELU:
-        launch_gn_fwd<SIR_ACT_LEAKY_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, w, bias, ms, eps, slope, R, ldr,
-                                                Y, ldy, mean, sd, drop);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
+        hipLaunchKernelGGL((k_gn_fwd<vw(), a(), dropped()>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, w,
+                           bias, ms, eps, slope, R, ldr, Y, ldy, mean, sd, d);
+    });
 }
 
-template <int ACT, bool DROP>
-void launch_gn_bwd(bool v4, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int F, int n_cc,
-                   const float* X, int64_t ldx, const float* dY, int64_t ldg, const float* w, const float* bias,
-                   const float* ms, const float* mean, const float* sd, float slope, float* dX, int64_t lddx,
-                   float* dw_part, float* dms_part, float* db_part, const Drop& drop) {
-    if (v4)
-        hipLaunchKernelGGL((k_gn_bwd<4, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY, ldg, w,
-                           bias, ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part, drop);
-    else
-        hipLaunchKernelGGL((k_gn_bwd<1, ACT, DROP>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY, ldg, w,
-                           bias, ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part, drop);
-}
-
-template <bool DROP>
-hipError_t gn_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* dY, int64_t ldg,
-                  const float* w, const float* bias, const float* ms, const float* mean, const float* sd, int act,
-                  float slope, float* dX, int64_t lddx, float* dw_part, float* dms_part, float* db_part,
-                  const Drop& drop, hipStream_t st) {
+hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* dY,
+                              int64_t ldg, const float* w, const float* bias, const float* ms, const float* mean,
+                              const float* sd, int act, float slope, float* dX, int64_t lddx, float* dw_part,
+                              float* dms_part, float* db_part, const Drop& drop, hipStream_t st) {
     if (B == 0) return hipSuccess;
     const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && al(X) && al(dY) && al(dX) &&
                     al(w) && al(bias) && al(ms) && al(mean) && al(sd) && al(dw_part) && al(dms_part) && al(db_part) &&
                     gn_wide(B, F);
-    const int vw = v4 ? 4 : 1;
-    const int n_cc = (F / vw + 63) / 64;
+    const int n_cc = (F / (v4 ? 4 : 1) + 63) / 64;
     const unsigned blocks = (unsigned)(B * n_cc);
-    switch (act) {
-    case SIR_ACT_IDENTITY:
-        launch_gn_bwd<SIR_ACT_IDENTITY, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd,
-                                              slope, dX, lddx, dw_part, dms_part, db_part, drop);
-        break;
-    case SIR_ACT_RELU:
-        launch_gn_bwd<SIR_ACT_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd, slope,
-                                          dX, lddx, dw_part, dms_part, db_part, drop);
-        break;
-    case SIR_ACT_LEAKY_RELU:
-        launch_gn_bwd<SIR_ACT_LEAKY_RELU, DROP>(v4, blocks, st, off, B, F, n_cc, X, ldx, dY, ldg, w, bias, ms, mean, sd,
-                                                slope, dX, lddx, dw_part, dms_part, db_part, drop);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-}  // namespace
-
-hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
-                              const float* w, const float* bias, const float* ms, float eps, int act, float slope,
-                              const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd,
-                              hipStream_t st) {
-    return gn_fwd<false>(off, B, F, X, ldx, w, bias, ms, eps, act, slope, R, ldr, Y, ldy, mean, sd, Drop(), st);
-}
-
-hipError_t run_graph_norm_drop_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* w,
-                                   const float* bias, const float* ms, float eps, int act, float slope, const float* R,
-                                   int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd, const Drop& drop,
-                                   hipStream_t st) {
-    if (!drop.on())
-        return gn_fwd<false>(off, B, F, X, ldx, w, bias, ms, eps, act, slope, R, ldr, Y, ldy, mean, sd, Drop(), st);
-    return gn_fwd<true>(off, B, F, X, ldx, w, bias, ms, eps, act, slope, R, ldr, Y, ldy, mean, sd, drop, st);
-}
-
-hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
-                              const float* dY, int64_t ldg, const float* w, const float* bias, const float* ms,
-                              const float* mean, const float* sd, int act, float slope, float* dX, int64_t lddx,
-                              float* dw_part, float* dms_part, float* db_part, hipStream_t st) {
-    return gn_bwd<false>(off, B, F, X, ldx, dY, ldg, w, bias, ms, mean, sd, act, slope, dX, lddx, dw_part, dms_part,
-                         db_part, Drop(), st);
-}
-
-hipError_t run_graph_norm_drop_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx, const float* dY,
-                                   int64_t ldg, const float* w, const float* bias, const float* ms, const float* mean,
-                                   const float* sd, int act, float slope, float* dX, int64_t lddx, float* dw_part,
-                                   float* dms_part, float* db_part, const Drop& drop, hipStream_t st) {
-    if (!drop.on())
-        return gn_bwd<false>(off, B, F, X, ldx, dY, ldg, w, bias, ms, mean, sd, act, slope, dX, lddx, dw_part, dms_part,
-                             db_part, Drop(), st);
-    return gn_bwd<true>(off, B, F, X, ldx, dY, ldg, w, bias, ms, mean, sd, act, slope, dX, lddx, dw_part, dms_part,
-                        db_part, drop, st);
+    return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
+        hipLaunchKernelGGL((k_gn_bwd<vw(), a(), dropped()>), dim3(blocks), dim3(64), 0, st, off, B, F, n_cc, X, ldx, dY,
+                           ldg, w, bias, ms, mean, sd, slope, dX, lddx, dw_part, dms_part, db_part, d);
+    });
 }
 
 }  // namespace sir

@@ -109,36 +109,15 @@ hipError_t run_resid_act_fwd(const void* Y, int64_t ldy, int dtype, const float*
 hipError_t run_resid_act_bwd(const float* D, int64_t ldd, const float* D2, int64_t ldd2, const void* Y, int64_t ldy,
                              int dtype, const float* R, int64_t ldr, void* DY, int64_t lddy, float* DR, int64_t lddr,
                              int64_t M, int N, int act, float slope, int order, hipStream_t st);
-hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
-                              const float* w, const float* bias, const float* ms, float eps, int act, float slope,
-                              const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd,
-                              hipStream_t st);
-hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float* X, int64_t ldx,
-                              const float* dY, int64_t ldg, const float* w, const float* bias, const float* ms,
-                              const float* mean, const float* sd, int act, float slope, float* dX, int64_t lddx,
-                              float* dw_part, float* dms_part, float* db_part, hipStream_t st);
 
-// BatchNorm1d / LayerNorm with the stack's activation and residual (sirconv_nodenorm.hip)
+// BatchNorm1d / LayerNorm (sirconv_nodenorm.hip): the statistics pass and the sizes; the fused norm -> activation ->
+// residual launchers of these and of GraphNorm are declared in sirconv_normdrop.h
 int64_t batch_norm_slabs(int64_t M);
 int64_t batch_norm_work_floats(int64_t M, int64_t N);
 hipError_t run_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int N, float eps, float momentum,
                                 float* run_mean, float* run_var, double* mean, double* invstd, float* work,
                                 hipStream_t st);
-hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
-                                  const double* invstd, const float* gamma, const float* beta, int act, float slope,
-                                  const float* R, int64_t ldr, float* Y, int64_t ldy, hipStream_t st);
-hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                  const double* mean, const double* invstd, const float* gamma, const float* beta,
-                                  int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
-                                  float* dbeta, float* work, hipStream_t st);
 int64_t layer_norm_parts(int64_t M);
-hipError_t run_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
-                                  const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
-                                  float* Y, int64_t ldy, float* mean, float* rstd, hipStream_t st);
-hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                  const float* gamma, const float* beta, const float* mean, const float* rstd,
-                                  int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
-                                  int64_t ldp, hipStream_t st);
 
 // graph readout: sum / mean / max pooling over the graphs of a batch and its backward (sirconv_readout.hip)
 int64_t graph_pool_slots(int64_t V, int64_t B);

@@ -33,6 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "sirconv.h"
 #include "sirconv_internal.h"
 #include "sirconv_normdrop.h"
@@ -44,36 +46,6 @@ constexpr int SLAB = SIR_BN_SLAB_ROWS;
 constexpr int BN_THREADS = 256;
 constexpr int FIN_SLICES = 64;      // k_bn_finish: 64 slices x 16 columns per block
 constexpr int FIN_COLS = 16;
-
-template <int VW>
-__device__ __forceinline__ void nld(float (&d)[VW], const float* __restrict__ p) {
-    if constexpr (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-        d[0] = p[0];
-    }
-}
-
-template <int VW>
-__device__ __forceinline__ void nst(float* __restrict__ p, const float (&s)[VW]) {
-    if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]);
-    else p[0] = s[0];
-}
-
-// torch's relu / leaky_relu and their backward (gn_act / gn_act_bwd of sirconv_graphnorm.hip)
-template <int ACT>
-__device__ __forceinline__ float nn_act(float y, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y <= 0.f ? 0.f : y;         // ReLU(NaN) = NaN, as torch.relu
-    else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? y : y * slope;
-    else return y;
-}
-template <int ACT>
-__device__ __forceinline__ float nn_act_bwd(float y, float g, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y > 0.f ? g : 0.f;
-    else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? g : g * slope;
-    else return g;
-}
 
 // (na, mean, m2) <- merge with (nb, bm, bq) (Chan et al.); nb > 0.  The statistics are carried in fp64 (as
 // torch's CPU BatchNorm accumulates them): mean and invstd come out correctly rounded, which is what keeps
@@ -120,7 +92,7 @@ k_bn_stats(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
             const int64_t left = (r1 - base + rs - 1) / rs;       // this thread's rows from `base` on
             const int nb = left < 8 ? (int)left : 8;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) nld<VW>(v[k], X + (base + (int64_t)(k < nb ? k : 0) * rs) * ldx + (int64_t)p.c * VW);
+            for (int k = 0; k < 8; ++k) vld<VW>(v[k], X + (base + (int64_t)(k < nb ? k : 0) * rs) * ldx + (int64_t)p.c * VW);
             const double nbf = (double)nb;
             double n2 = na;
 #pragma unroll
@@ -271,8 +243,8 @@ k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int64_t row = base + (int64_t)k * rs < r1 ? base + (int64_t)k * rs : base;
-            nld<VW>(v[k], X + row * ldx + col);
-            if (R != nullptr) nld<VW>(r[k], R + row * ldr + col);
+            vld<VW>(v[k], X + row * ldx + col);
+            if (R != nullptr) vld<VW>(r[k], R + row * ldr + col);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -284,11 +256,11 @@ k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
 #pragma unroll
                 for (int x = 0; x < VW; ++x) {
                     const float y = (float)(((double)v[k][x] - mu[x]) * a[x] + b[x]);
-                    o[x] = nn_act<ACT>(y, slope);
+                    o[x] = norm_act<ACT>(y, slope);
                     if constexpr (DROP) o[x] = drop_keep(drop, rh, (int)col + x) ? o[x] * drop.scale : 0.f;
                     if (R != nullptr) o[x] = o[x] + r[k][x];
                 }
-                nst<VW>(Y + row * ldy + col, o);
+                vst<VW>(Y + row * ldy + col, o);
             }
         }
     }
@@ -319,8 +291,8 @@ k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int64_t row = base + (int64_t)k * rs < r1 ? base + (int64_t)k * rs : base;
-                nld<VW>(v[k], X + row * ldx + col);
-                nld<VW>(d[k], D + row * ldg + col);
+                vld<VW>(v[k], X + row * ldx + col);
+                vld<VW>(d[k], D + row * ldg + col);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -333,7 +305,7 @@ k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__
                         const float y = (float)(c * a[x] + b[x]);
                         float g0 = d[k][x];
                         if constexpr (DROP) g0 = drop_keep(drop, rh, (int)col + x) ? g0 * drop.scale : 0.f;
-                        const float gg = nn_act_bwd<ACT>(y, g0, slope);
+                        const float gg = norm_act_bwd<ACT>(y, g0, slope);
                         sb[x] += (double)gg;
                         sg[x] += (double)gg * c;
                     }
@@ -385,8 +357,8 @@ k_bn_bwd_app(const float* __restrict__ X, int64_t ldx, const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int64_t row = base + (int64_t)k * rs < r1 ? base + (int64_t)k * rs : base;
-            nld<VW>(v[k], X + row * ldx + col);
-            nld<VW>(d[k], D + row * ldg + col);
+            vld<VW>(v[k], X + row * ldx + col);
+            vld<VW>(d[k], D + row * ldg + col);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -401,10 +373,10 @@ k_bn_bwd_app(const float* __restrict__ X, int64_t ldx, const float* __restrict__
                     const float y = (float)(c * a[x] + b[x]);
                     float g0 = d[k][x];
                     if constexpr (DROP) g0 = drop_keep(drop, rh, (int)col + x) ? g0 * drop.scale : 0.f;
-                    const float gg = nn_act_bwd<ACT>(y, g0, slope);
+                    const float gg = norm_act_bwd<ACT>(y, g0, slope);
                     o[x] = (float)((((double)gg - gm[x]) - c * kk[x]) * a[x]);
                 }
-                nst<VW>(dX + row * lddx + col, o);
+                vst<VW>(dX + row * lddx + col, o);
             }
         }
     }
@@ -442,7 +414,7 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
         on[j] = c < N;
 #pragma unroll
         for (int x = 0; x < VW; ++x) { g[j][x] = 0.f; b[j][x] = 0.f; }
-        if (on[j]) { nld<VW>(g[j], gamma + c); nld<VW>(b[j], beta + c); }
+        if (on[j]) { vld<VW>(g[j], gamma + c); vld<VW>(b[j], beta + c); }
     }
     for (int64_t r = r0; r < r1; r += RB) {
         float v[RB][NCH][VW], rr[RB][NCH][VW];
@@ -454,8 +426,8 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
 #pragma unroll
                 for (int x = 0; x < VW; ++x) { v[k][j][x] = 0.f; rr[k][j][x] = 0.f; }
                 if (on[j]) {
-                    nld<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
-                    if (R != nullptr) nld<VW>(rr[k][j], R + row * ldr + (j * 64 + lane) * VW);
+                    vld<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
+                    if (R != nullptr) vld<VW>(rr[k][j], R + row * ldr + (j * 64 + lane) * VW);
                 }
             }
         }
@@ -486,12 +458,12 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
 #pragma unroll
                         for (int x = 0; x < VW; ++x) {
                             const float y = (v[k][j][x] - mu) * rstd * g[j][x] + b[j][x];
-                            o[x] = nn_act<ACT>(y, slope);
+                            o[x] = norm_act<ACT>(y, slope);
                             if constexpr (DROP)
                                 o[x] = drop_keep(drop, rh, (j * 64 + lane) * VW + x) ? o[x] * drop.scale : 0.f;
                             if (R != nullptr) o[x] = o[x] + rr[k][j][x];
                         }
-                        nst<VW>(Y + (r + k) * ldy + (j * 64 + lane) * VW, o);
+                        vst<VW>(Y + (r + k) * ldy + (j * 64 + lane) * VW, o);
                     }
                 }
                 if (lane == 0) { mean_out[r + k] = mu; rstd_out[r + k] = rstd; }
@@ -520,7 +492,7 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
         on[j] = c < N;
 #pragma unroll
         for (int x = 0; x < VW; ++x) { g[j][x] = 0.f; b[j][x] = 0.f; dw[j][x] = 0.f; db[j][x] = 0.f; }
-        if (on[j]) { nld<VW>(g[j], gamma + c); nld<VW>(b[j], beta + c); }
+        if (on[j]) { vld<VW>(g[j], gamma + c); vld<VW>(b[j], beta + c); }
     }
     for (int64_t r = r0; r < r1; r += RB) {
         float v[RB][NCH][VW], d[RB][NCH][VW], mu[RB], rs[RB];
@@ -534,8 +506,8 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
 #pragma unroll
                 for (int x = 0; x < VW; ++x) { v[k][j][x] = 0.f; d[k][j][x] = 0.f; }
                 if (on[j]) {
-                    nld<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
-                    nld<VW>(d[k][j], D + row * ldg + (j * 64 + lane) * VW);
+                    vld<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
+                    vld<VW>(d[k][j], D + row * ldg + (j * 64 + lane) * VW);
                 }
             }
         }
@@ -554,7 +526,7 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
                         const float y = xh[j][x] * g[j][x] + b[j][x];
                         float g0 = d[k][j][x];
                         if constexpr (DROP) g0 = drop_keep(drop, rh, (j * 64 + lane) * VW + x) ? g0 * drop.scale : 0.f;
-                        const float gg = on[j] ? nn_act_bwd<ACT>(y, g0, slope) : 0.f;
+                        const float gg = on[j] ? norm_act_bwd<ACT>(y, g0, slope) : 0.f;
                         db[j][x] += gg;
                         dw[j][x] += gg * xh[j][x];
                         a[j][x] = gg * g[j][x];
@@ -570,7 +542,7 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
                         float o[VW];
 #pragma unroll
                         for (int x = 0; x < VW; ++x) o[x] = rs[k] * ((a[j][x] - m1) - xh[j][x] * m2);
-                        nst<VW>(dX + (r + k) * lddx + (j * 64 + lane) * VW, o);
+                        vst<VW>(dX + (r + k) * lddx + (j * 64 + lane) * VW, o);
                     }
                 }
             }
@@ -579,13 +551,11 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
         if (on[j]) {
-            nst<VW>(dw_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, dw[j]);
-            nst<VW>(db_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, db[j]);
+            vst<VW>(dw_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, dw[j]);
+            vst<VW>(db_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, db[j]);
         }
     }
 }
-
-bool al(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // block geometry of the BatchNorm kernels: column chunks of cwv vectors, rs row slices (rs * cwv <= 256)
 struct BnGeom {
@@ -603,14 +573,6 @@ BnGeom bn_geom(int64_t M, int N, bool v4) {
     g.grid = dim3((unsigned)((M + SLAB - 1) / SLAB), (unsigned)chunks);
     return g;
 }
-
-#define SIR_NN_ACT_SWITCH(act, CALL)                                   \
-    switch (act) {                                                     \
-    case SIR_ACT_IDENTITY: CALL(SIR_ACT_IDENTITY); break;              \
-    case SIR_ACT_RELU: CALL(SIR_ACT_RELU); break;                      \
-    case SIR_ACT_LEAKY_RELU: CALL(SIR_ACT_LEAKY_RELU); break;          \
-    default: return hipErrorInvalidValue;                              \
-    }
 
 }  // namespace
 
@@ -637,34 +599,24 @@ hipError_t run_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int N, f
     return hipGetLastError();
 }
 
-
-namespace {
-
-template <bool DROP>
-hipError_t bn_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean, const double* invstd,
-                      const float* gamma, const float* beta, int act, float slope, const float* R, int64_t ldr,
-                      float* Y, int64_t ldy, const Drop& drop, hipStream_t st) {
+hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
+                                  const double* invstd, const float* gamma, const float* beta, int act, float slope,
+                                  const float* R, int64_t ldr, float* Y, int64_t ldy, const Drop& drop,
+                                  hipStream_t st) {
     if (M == 0) return hipSuccess;
     const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
                     al(R);
     const BnGeom g = bn_geom(M, N, v4);
-#define CALL(A)                                                                                                        \
-    if (v4)                                                                                                            \
-        hipLaunchKernelGGL((k_bn_apply<4, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, mean,  \
-                           invstd, gamma, beta, slope, R, ldr, Y, ldy, drop);                                          \
-    else                                                                                                               \
-        hipLaunchKernelGGL((k_bn_apply<1, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, mean,  \
-                           invstd, gamma, beta, slope, R, ldr, Y, ldy, drop)
-    SIR_NN_ACT_SWITCH(act, CALL)
-#undef CALL
-    return hipGetLastError();
+    return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
+        hipLaunchKernelGGL((k_bn_apply<vw(), a(), dropped()>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv,
+                           g.rs, mean, invstd, gamma, beta, slope, R, ldr, Y, ldy, d);
+    });
 }
 
-template <bool DROP>
-hipError_t bn_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N, const double* mean,
-                      const double* invstd, const float* gamma, const float* beta, int act, float slope, int training,
-                      float* dX, int64_t lddx, float* dgamma, float* dbeta, float* work, const Drop& drop,
-                      hipStream_t st) {
+hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
+                                  const double* mean, const double* invstd, const float* gamma, const float* beta,
+                                  int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
+                                  float* dbeta, float* work, const Drop& drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
     const int64_t S = batch_norm_slabs(M);
     double* pdb = reinterpret_cast<double*>(work);
@@ -673,63 +625,20 @@ hipError_t bn_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, 
     double* kdot = gmean + N;
     const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && al(X) && al(D) && al(dX);
     const BnGeom g = bn_geom(M, N, v4);
-#define CALL(A)                                                                                                        \
-    if (v4)                                                                                                            \
-        hipLaunchKernelGGL((k_bn_bwd_red<4, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
-                           g.rs, mean, invstd, gamma, beta, slope, pdb, pdg, drop);                                    \
-    else                                                                                                               \
-        hipLaunchKernelGGL((k_bn_bwd_red<1, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
-                           g.rs, mean, invstd, gamma, beta, slope, pdb, pdg, drop)
-    SIR_NN_ACT_SWITCH(act, CALL)
-#undef CALL
-    hipLaunchKernelGGL((k_bn_finish<false>), dim3((unsigned)((N + FIN_COLS - 1) / FIN_COLS)),
-                       dim3(FIN_SLICES * FIN_COLS), 0, st, pdb, pdg, S, M, N, 0.f, 0.f, nullptr, nullptr, invstd, dbeta,
-                       dgamma, gmean, kdot);
-#define CALL(A)                                                                                                        \
-    if (v4)                                                                                                            \
-        hipLaunchKernelGGL((k_bn_bwd_app<4, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
-                           g.rs, mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx, drop);             \
-    else                                                                                                               \
-        hipLaunchKernelGGL((k_bn_bwd_app<1, A, DROP>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M, N, g.cwv,    \
-                           g.rs, mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx, drop)
-    SIR_NN_ACT_SWITCH(act, CALL)
-#undef CALL
-    return hipGetLastError();
-}
-
-}  // namespace
-
-hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
-                                  const double* invstd, const float* gamma, const float* beta, int act, float slope,
-                                  const float* R, int64_t ldr, float* Y, int64_t ldy, hipStream_t st) {
-    return bn_act_fwd<false>(X, ldx, M, N, mean, invstd, gamma, beta, act, slope, R, ldr, Y, ldy, Drop(), st);
-}
-
-hipError_t run_batch_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int N, const double* mean,
-                                       const double* invstd, const float* gamma, const float* beta, int act,
-                                       float slope, const float* R, int64_t ldr, float* Y, int64_t ldy,
-                                       const Drop& drop, hipStream_t st) {
-    if (!drop.on()) return bn_act_fwd<false>(X, ldx, M, N, mean, invstd, gamma, beta, act, slope, R, ldr, Y, ldy, Drop(), st);
-    return bn_act_fwd<true>(X, ldx, M, N, mean, invstd, gamma, beta, act, slope, R, ldr, Y, ldy, drop, st);
-}
-
-hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                  const double* mean, const double* invstd, const float* gamma, const float* beta,
-                                  int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
-                                  float* dbeta, float* work, hipStream_t st) {
-    return bn_act_bwd<false>(X, ldx, D, ldg, M, N, mean, invstd, gamma, beta, act, slope, training, dX, lddx, dgamma,
-                             dbeta, work, Drop(), st);
-}
-
-hipError_t run_batch_norm_act_drop_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                       const double* mean, const double* invstd, const float* gamma, const float* beta,
-                                       int act, float slope, int training, float* dX, int64_t lddx, float* dgamma,
-                                       float* dbeta, float* work, const Drop& drop, hipStream_t st) {
-    if (!drop.on())
-        return bn_act_bwd<false>(X, ldx, D, ldg, M, N, mean, invstd, gamma, beta, act, slope, training, dX, lddx, dgamma,
-                                 dbeta, work, Drop(), st);
-    return bn_act_bwd<true>(X, ldx, D, ldg, M, N, mean, invstd, gamma, beta, act, slope, training, dX, lddx, dgamma,
-                            dbeta, work, drop, st);
+    return by_drop(drop, [&](auto dropped, const Drop& d) {
+        const hipError_t err = by_act_vw(act, v4, [&](auto a, auto vw) {
+            hipLaunchKernelGGL((k_bn_bwd_red<vw(), a(), dropped()>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M,
+                               N, g.cwv, g.rs, mean, invstd, gamma, beta, slope, pdb, pdg, d);
+        });
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL((k_bn_finish<false>), dim3((unsigned)((N + FIN_COLS - 1) / FIN_COLS)),
+                           dim3(FIN_SLICES * FIN_COLS), 0, st, pdb, pdg, S, M, N, 0.f, 0.f, nullptr, nullptr, invstd,
+                           dbeta, dgamma, gmean, kdot);
+        return by_act_vw(act, v4, [&](auto a, auto vw) {
+            hipLaunchKernelGGL((k_bn_bwd_app<vw(), a(), dropped()>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, D, ldg, M,
+                               N, g.cwv, g.rs, mean, invstd, gamma, beta, slope, gmean, kdot, training, dX, lddx, d);
+        });
+    });
 }
 
 // rows per wave (= per partial row of the backward): a function of M alone
@@ -744,120 +653,57 @@ int64_t layer_norm_parts(int64_t M) {
 
 namespace {
 
-// NCH: float4 rows 1, 2 or 4 vectors per lane (N <= 256, 512, 1024); scalar rows 1, 2, 4, 8 or 16
-template <int ACT, bool DROP>
-hipError_t launch_ln_fwd(bool v4, int N, unsigned blocks, hipStream_t st, const float* X, int64_t ldx, int64_t M,
-                         int64_t rpw, const float* gamma, const float* beta, float eps, float slope, const float* R,
-                         int64_t ldr, float* Y, int64_t ldy, float* mean, float* rstd, const Drop& drop) {
-#define LNF(VW, NCH)                                                                                                  \
-    hipLaunchKernelGGL((k_ln_fwd<VW, NCH, ACT, DROP>), dim3(blocks), dim3(64), 0, st, X, ldx, M, N, rpw, gamma, beta, \
-                       eps, slope, R, ldr, Y, ldy, mean, rstd, drop)
-    if (v4) {
-        if (N <= 256) LNF(4, 1);
-        else if (N <= 512) LNF(4, 2);
-        else LNF(4, 4);
+// NCH: float4 rows 1, 2 or 4 vectors per lane (N <= 256, 512, 1024); scalar rows 1, 2, 4, 8 or 16.
+// go(NCH) launches the kernel of width VW with that many vectors per lane.
+template <int VW, typename Fn>
+void ln_by_nch(int N, Fn&& go) {
+    if constexpr (VW == 4) {
+        if (N <= 256) go(std::integral_constant<int, 1>());
+        else if (N <= 512) go(std::integral_constant<int, 2>());
+        else go(std::integral_constant<int, 4>());
     } else {
-        if (N <= 64) LNF(1, 1);
-        else if (N <= 128) LNF(1, 2);
-        else if (N <= 256) LNF(1, 4);
-        else if (N <= 512) LNF(1, 8);
-        else LNF(1, 16);
+        if (N <= 64) go(std::integral_constant<int, 1>());
+        else if (N <= 128) go(std::integral_constant<int, 2>());
+        else if (N <= 256) go(std::integral_constant<int, 4>());
+        else if (N <= 512) go(std::integral_constant<int, 8>());
+        else go(std::integral_constant<int, 16>());
     }
-#undef LNF
-    return hipGetLastError();
-}
-
-template <int ACT, bool DROP>
-hipError_t launch_ln_bwd(bool v4, int N, unsigned blocks, hipStream_t st, const float* X, int64_t ldx, const float* D,
-                         int64_t ldg, int64_t M, int64_t rpw, const float* gamma, const float* beta, const float* mean,
-                         const float* rstd, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
-                         int64_t ldp, const Drop& drop) {
-#define LNB(VW, NCH)                                                                                                  \
-    hipLaunchKernelGGL((k_ln_bwd<VW, NCH, ACT, DROP>), dim3(blocks), dim3(64), 0, st, X, ldx, D, ldg, M, N, rpw,      \
-                       gamma, beta, mean, rstd, slope, dX, lddx, dw_part, db_part, ldp, drop)
-    if (v4) {
-        if (N <= 256) LNB(4, 1);
-        else if (N <= 512) LNB(4, 2);
-        else LNB(4, 4);
-    } else {
-        if (N <= 64) LNB(1, 1);
-        else if (N <= 128) LNB(1, 2);
-        else if (N <= 256) LNB(1, 4);
-        else if (N <= 512) LNB(1, 8);
-        else LNB(1, 16);
-    }
-#undef LNB
-    return hipGetLastError();
-}
-
-template <bool DROP>
-hipError_t ln_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma, const float* beta, float eps,
-                      int act, float slope, const float* R, int64_t ldr, float* Y, int64_t ldy, float* mean,
-                      float* rstd, const Drop& drop, hipStream_t st) {
-    if (M == 0) return hipSuccess;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
-                    al(R) && al(gamma) && al(beta);
-    const int64_t rpw = layer_norm_rows_per_part(M);
-    const unsigned blocks = (unsigned)layer_norm_parts(M);
-#define CALL(A)                                                                                                        \
-    return launch_ln_fwd<A, DROP>(v4, N, blocks, st, X, ldx, M, rpw, gamma, beta, eps, slope, R, ldr, Y, ldy, mean, rstd, \
-                                  drop)
-    SIR_NN_ACT_SWITCH(act, CALL)
-#undef CALL
-    return hipSuccess;
-}
-
-template <bool DROP>
-hipError_t ln_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N, const float* gamma,
-                      const float* beta, const float* mean, const float* rstd, int act, float slope, float* dX,
-                      int64_t lddx, float* dw_part, float* db_part, int64_t ldp, const Drop& drop, hipStream_t st) {
-    if (M == 0) return hipSuccess;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && ldp % 4 == 0 && al(X) && al(D) &&
-                    al(dX) && al(gamma) && al(beta) && al(dw_part) && al(db_part);
-    const int64_t rpw = layer_norm_rows_per_part(M);
-    const unsigned blocks = (unsigned)layer_norm_parts(M);
-#define CALL(A)                                                                                                        \
-    return launch_ln_bwd<A, DROP>(v4, N, blocks, st, X, ldx, D, ldg, M, rpw, gamma, beta, mean, rstd, slope, dX, lddx,  \
-                                  dw_part, db_part, ldp, drop)
-    SIR_NN_ACT_SWITCH(act, CALL)
-#undef CALL
-    return hipSuccess;
 }
 
 }  // namespace
 
 hipError_t run_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
                                   const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
-                                  float* Y, int64_t ldy, float* mean, float* rstd, hipStream_t st) {
-    return ln_act_fwd<false>(X, ldx, M, N, gamma, beta, eps, act, slope, R, ldr, Y, ldy, mean, rstd, Drop(), st);
-}
-
-hipError_t run_layer_norm_act_drop_fwd(const float* X, int64_t ldx, int64_t M, int N, const float* gamma,
-                                       const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
-                                       float* Y, int64_t ldy, float* mean, float* rstd, const Drop& drop,
-                                       hipStream_t st) {
-    if (!drop.on())
-        return ln_act_fwd<false>(X, ldx, M, N, gamma, beta, eps, act, slope, R, ldr, Y, ldy, mean, rstd, Drop(), st);
-    return ln_act_fwd<true>(X, ldx, M, N, gamma, beta, eps, act, slope, R, ldr, Y, ldy, mean, rstd, drop, st);
+                                  float* Y, int64_t ldy, float* mean, float* rstd, const Drop& drop, hipStream_t st) {
+    if (M == 0) return hipSuccess;
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
+                    al(R) && al(gamma) && al(beta);
+    const int64_t rpw = layer_norm_rows_per_part(M);
+    const unsigned blocks = (unsigned)layer_norm_parts(M);
+    return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
+        ln_by_nch<vw()>(N, [&](auto nch) {
+            hipLaunchKernelGGL((k_ln_fwd<vw(), nch(), a(), dropped()>), dim3(blocks), dim3(64), 0, st, X, ldx, M, N, rpw,
+                               gamma, beta, eps, slope, R, ldr, Y, ldy, mean, rstd, d);
+        });
+    });
 }
 
 hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
                                   const float* gamma, const float* beta, const float* mean, const float* rstd,
                                   int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
-                                  int64_t ldp, hipStream_t st) {
-    return ln_act_bwd<false>(X, ldx, D, ldg, M, N, gamma, beta, mean, rstd, act, slope, dX, lddx, dw_part, db_part, ldp,
-                             Drop(), st);
-}
-
-hipError_t run_layer_norm_act_drop_bwd(const float* X, int64_t ldx, const float* D, int64_t ldg, int64_t M, int N,
-                                       const float* gamma, const float* beta, const float* mean, const float* rstd,
-                                       int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
-                                       int64_t ldp, const Drop& drop, hipStream_t st) {
-    if (!drop.on())
-        return ln_act_bwd<false>(X, ldx, D, ldg, M, N, gamma, beta, mean, rstd, act, slope, dX, lddx, dw_part, db_part,
-                                 ldp, Drop(), st);
-    return ln_act_bwd<true>(X, ldx, D, ldg, M, N, gamma, beta, mean, rstd, act, slope, dX, lddx, dw_part, db_part, ldp,
-                            drop, st);
+                                  int64_t ldp, const Drop& drop, hipStream_t st) {
+    if (M == 0) return hipSuccess;
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && ldp % 4 == 0 && al(X) && al(D) &&
+                    al(dX) && al(gamma) && al(beta) && al(dw_part) && al(db_part);
+    const int64_t rpw = layer_norm_rows_per_part(M);
+    const unsigned blocks = (unsigned)layer_norm_parts(M);
+    return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
+        ln_by_nch<vw()>(N, [&](auto nch) {
+            hipLaunchKernelGGL((k_ln_bwd<vw(), nch(), a(), dropped()>), dim3(blocks), dim3(64), 0, st, X, ldx, D, ldg, M,
+                               N, rpw, gamma, beta, mean, rstd, slope, dX, lddx, dw_part, db_part, ldp, d);
+        });
+    });
 }
 
 }  // namespace sir
+

@@ -154,6 +154,14 @@ def _drop(drop):
     return ctypes.byref(Dropout(int(seed) & (2 ** 64 - 1), float(p), None))
 
 
+def _call_drop(plain, dropped, drop, *args):
+    """rc of a fused norm entry: ``plain(*args)`` without a layer dropout, else its ``*_drop_*`` sibling,
+    which takes the ``sir_dropout_t*`` before the trailing stream argument."""
+    if drop is None:
+        return plain(*args)
+    return dropped(*args[:-1], _drop(drop), args[-1])
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -541,53 +549,31 @@ def resid_act_bwd(D, Y, R, act, slope, order, dY, dR=None, D2=None):
     _check(rc, lib)
 
 
-def graph_norm_act_fwd(off, X, weight, bias, mean_scale, eps, act, slope, R, Y, mean, std):
-    """GraphNorm -> act -> + R in one kernel (``sir_graph_norm_act_fwd``; R may be None)."""
+def graph_norm_act_fwd(off, X, weight, bias, mean_scale, eps, act, slope, R, Y, mean, std, drop=None):
+    """GraphNorm -> act -> + R in one kernel (``sir_graph_norm_act_fwd``; R may be None).  ``drop`` = (seed, p)
+    as for :func:`dropout_apply`: the layer dropout between the activation and the add
+    (``sir_graph_norm_act_drop_fwd``), the bits of an [V, F] block at col0 = 0."""
     lib = load()
     B, F = mean.shape
     with _Timed("sir_graph_norm_fwd", Y.device):
-        rc = lib.sir_graph_norm_act_fwd(_ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(weight), _ptr(bias),
-                                        _ptr(mean_scale), float(eps), int(act), float(slope), _ptr(R),
-                                        _ld(R, F) if R is not None else 0, _ptr(Y), _ld(Y, F), _ptr(mean), _ptr(std),
-                                        _stream(Y.device))
+        rc = _call_drop(lib.sir_graph_norm_act_fwd, lib.sir_graph_norm_act_drop_fwd, drop,
+                        _ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(weight), _ptr(bias), _ptr(mean_scale), float(eps),
+                        int(act), float(slope), _ptr(R), _ld(R, F) if R is not None else 0, _ptr(Y), _ld(Y, F),
+                        _ptr(mean), _ptr(std), _stream(Y.device))
     _check(rc, lib)
 
 
-def graph_norm_act_bwd(off, X, dY, weight, bias, mean_scale, mean, std, act, slope, dX, dw_part, dms_part, db_part):
-    """Backward of :func:`graph_norm_act_fwd` (dY: the gradient of its output)."""
+def graph_norm_act_bwd(off, X, dY, weight, bias, mean_scale, mean, std, act, slope, dX, dw_part, dms_part, db_part,
+                       drop=None):
+    """Backward of :func:`graph_norm_act_fwd` (dY: the gradient of its output; the same ``drop``: the mask is
+    recomputed)."""
     lib = load()
     B, F = mean.shape
     with _Timed("sir_graph_norm_bwd", dX.device):
-        rc = lib.sir_graph_norm_act_bwd(_ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(dY), _ld(dY, F), _ptr(weight),
-                                        _ptr(bias), _ptr(mean_scale), _ptr(mean), _ptr(std), int(act), float(slope),
-                                        _ptr(dX), _ld(dX, F), _ptr(dw_part), _ptr(dms_part), _ptr(db_part),
-                                        _stream(dX.device))
-    _check(rc, lib)
-
-
-def graph_norm_act_drop_fwd(off, X, weight, bias, mean_scale, eps, act, slope, R, Y, mean, std, drop):
-    """GraphNorm -> act -> layer dropout -> + R in one kernel (``sir_graph_norm_act_drop_fwd``); ``drop`` =
-    (seed, p) as for :func:`dropout_apply`, the bits of an [V, F] block at col0 = 0."""
-    lib = load()
-    B, F = mean.shape
-    with _Timed("sir_graph_norm_fwd", Y.device):
-        rc = lib.sir_graph_norm_act_drop_fwd(_ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(weight), _ptr(bias),
-                                             _ptr(mean_scale), float(eps), int(act), float(slope), _ptr(R),
-                                             _ld(R, F) if R is not None else 0, _ptr(Y), _ld(Y, F), _ptr(mean),
-                                             _ptr(std), _drop(drop), _stream(Y.device))
-    _check(rc, lib)
-
-
-def graph_norm_act_drop_bwd(off, X, dY, weight, bias, mean_scale, mean, std, act, slope, dX, dw_part, dms_part, db_part,
-                            drop):
-    """Backward of :func:`graph_norm_act_drop_fwd` (the same ``drop``: the mask is recomputed)."""
-    lib = load()
-    B, F = mean.shape
-    with _Timed("sir_graph_norm_bwd", dX.device):
-        rc = lib.sir_graph_norm_act_drop_bwd(_ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(dY), _ld(dY, F), _ptr(weight),
-                                             _ptr(bias), _ptr(mean_scale), _ptr(mean), _ptr(std), int(act),
-                                             float(slope), _ptr(dX), _ld(dX, F), _ptr(dw_part), _ptr(dms_part),
-                                             _ptr(db_part), _drop(drop), _stream(dX.device))
+        rc = _call_drop(lib.sir_graph_norm_act_bwd, lib.sir_graph_norm_act_drop_bwd, drop,
+                        _ptr(off), B, F, _ptr(X), _ld(X, F), _ptr(dY), _ld(dY, F), _ptr(weight), _ptr(bias),
+                        _ptr(mean_scale), _ptr(mean), _ptr(std), int(act), float(slope), _ptr(dX), _ld(dX, F),
+                        _ptr(dw_part), _ptr(dms_part), _ptr(db_part), _stream(dX.device))
     _check(rc, lib)
 
 
@@ -624,51 +610,29 @@ def batch_norm_stats(X, eps, momentum, running_mean, running_var, mean, invstd, 
     _check(rc, lib)
 
 
-def batch_norm_act_fwd(X, mean, invstd, weight, bias, act, slope, R, Y):
-    """Y = act((X - mean) invstd weight + bias) + R in one pass (``sir_batch_norm_act_fwd``; R may be None)."""
+def batch_norm_act_fwd(X, mean, invstd, weight, bias, act, slope, R, Y, drop=None):
+    """Y = act((X - mean) invstd weight + bias) + R in one pass (``sir_batch_norm_act_fwd``; R may be None).
+    ``drop`` = (seed, p): the layer dropout between the activation and the add of R
+    (``sir_batch_norm_act_drop_fwd``), the bits of an [M, N] block at col0 = 0."""
     lib = load()
     M, N = X.shape
     with _Timed("sir_batch_norm_act_fwd", X.device):
-        rc = lib.sir_batch_norm_act_fwd(_ptr(X), _ld(X, N), M, N, _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias),
-                                        int(act), float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y),
-                                        _ld(Y, N), _stream(X.device))
+        rc = _call_drop(lib.sir_batch_norm_act_fwd, lib.sir_batch_norm_act_drop_fwd, drop,
+                        _ptr(X), _ld(X, N), M, N, _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), int(act),
+                        float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y), _ld(Y, N), _stream(X.device))
     _check(rc, lib)
 
 
-def batch_norm_act_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, dX, dweight, dbias, work):
-    """Backward of :func:`batch_norm_act_fwd` (``sir_batch_norm_act_bwd``): dX, dweight, dbias."""
+def batch_norm_act_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, dX, dweight, dbias, work, drop=None):
+    """Backward of :func:`batch_norm_act_fwd` (``sir_batch_norm_act_bwd``): dX, dweight, dbias (the same
+    ``drop``: the mask is recomputed, ``sir_batch_norm_act_drop_bwd``)."""
     lib = load()
     M, N = X.shape
     with _Timed("sir_batch_norm_act_bwd", X.device):
-        rc = lib.sir_batch_norm_act_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(mean), _ptr(invstd),
-                                        _ptr(weight), _ptr(bias), int(act), float(slope), int(bool(training)),
-                                        _ptr(dX), _ld(dX, N), _ptr(dweight), _ptr(dbias), _ptr(work),
-                                        _stream(X.device))
-    _check(rc, lib)
-
-
-def batch_norm_act_drop_fwd(X, mean, invstd, weight, bias, act, slope, R, Y, drop):
-    """:func:`batch_norm_act_fwd` with the layer dropout between the activation and the add of R
-    (``sir_batch_norm_act_drop_fwd``); ``drop`` = (seed, p), the bits of an [M, N] block at col0 = 0."""
-    lib = load()
-    M, N = X.shape
-    with _Timed("sir_batch_norm_act_fwd", X.device):
-        rc = lib.sir_batch_norm_act_drop_fwd(_ptr(X), _ld(X, N), M, N, _ptr(mean), _ptr(invstd), _ptr(weight),
-                                             _ptr(bias), int(act), float(slope), _ptr(R),
-                                             _ld(R, N) if R is not None else 0, _ptr(Y), _ld(Y, N), _drop(drop),
-                                             _stream(X.device))
-    _check(rc, lib)
-
-
-def batch_norm_act_drop_bwd(X, dY, mean, invstd, weight, bias, act, slope, training, dX, dweight, dbias, work, drop):
-    """Backward of :func:`batch_norm_act_drop_fwd` (the same ``drop``: the mask is recomputed)."""
-    lib = load()
-    M, N = X.shape
-    with _Timed("sir_batch_norm_act_bwd", X.device):
-        rc = lib.sir_batch_norm_act_drop_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(mean), _ptr(invstd),
-                                             _ptr(weight), _ptr(bias), int(act), float(slope), int(bool(training)),
-                                             _ptr(dX), _ld(dX, N), _ptr(dweight), _ptr(dbias), _ptr(work),
-                                             _drop(drop), _stream(X.device))
+        rc = _call_drop(lib.sir_batch_norm_act_bwd, lib.sir_batch_norm_act_drop_bwd, drop,
+                        _ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(mean), _ptr(invstd), _ptr(weight),
+                        _ptr(bias), int(act), float(slope), int(bool(training)), _ptr(dX), _ld(dX, N), _ptr(dweight),
+                        _ptr(dbias), _ptr(work), _stream(X.device))
     _check(rc, lib)
 
 
@@ -739,20 +703,24 @@ def graph_pool_bwd(off, dP, op, dX, arg=None):
         _check(rc, lib)
 
 
-def layer_norm_act_fwd(X, weight, bias, eps, act, slope, R, Y, mean, rstd):
-    """Y = act(LayerNorm(X)) + R in one pass (``sir_layer_norm_act_fwd``); mean / rstd [M] for the backward."""
+def layer_norm_act_fwd(X, weight, bias, eps, act, slope, R, Y, mean, rstd, drop=None):
+    """Y = act(LayerNorm(X)) + R in one pass (``sir_layer_norm_act_fwd``); mean / rstd [M] for the backward.
+    ``drop`` = (seed, p): the layer dropout between the activation and the add of R
+    (``sir_layer_norm_act_drop_fwd``), the bits of an [M, N] block at col0 = 0."""
     lib = load()
     M, N = X.shape
     with _Timed("sir_layer_norm_act_fwd", X.device):
-        rc = lib.sir_layer_norm_act_fwd(_ptr(X), _ld(X, N), M, N, _ptr(weight), _ptr(bias), float(eps), int(act),
-                                        float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y), _ld(Y, N),
-                                        _ptr(mean), _ptr(rstd), _stream(X.device))
+        rc = _call_drop(lib.sir_layer_norm_act_fwd, lib.sir_layer_norm_act_drop_fwd, drop,
+                        _ptr(X), _ld(X, N), M, N, _ptr(weight), _ptr(bias), float(eps), int(act), float(slope),
+                        _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y), _ld(Y, N), _ptr(mean), _ptr(rstd),
+                        _stream(X.device))
     _check(rc, lib)
 
 
-def layer_norm_act_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX):
-    """Backward of :func:`layer_norm_act_fwd`: writes dX, returns (dweight, dbias) — the per-slab partial
-    rows of ``sir_layer_norm_act_bwd`` summed in slab order by ``sir_col_sum``."""
+def layer_norm_act_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX, drop=None):
+    """Backward of :func:`layer_norm_act_fwd` (the same ``drop``): writes dX, returns (dweight, dbias) — the
+    per-slab partial rows of ``sir_layer_norm_act_bwd`` / ``sir_layer_norm_act_drop_bwd`` summed in slab order
+    by ``sir_col_sum``."""
     lib = load()
     M, N = X.shape
     parts = int(lib.sir_layer_norm_bwd_parts(M, N))
@@ -762,43 +730,12 @@ def layer_norm_act_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX):
     part = torch.empty((max(parts, 1), 2 * npad), device=X.device, dtype=torch.float32)
     db_part = part[:, npad:]
     with _Timed("sir_layer_norm_act_bwd", X.device):
-        rc = lib.sir_layer_norm_act_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(weight), _ptr(bias),
-                                        _ptr(mean), _ptr(rstd), int(act), float(slope), _ptr(dX), _ld(dX, N),
-                                        _ptr(part), _ptr(db_part), 2 * npad, _stream(X.device))
+        rc = _call_drop(lib.sir_layer_norm_act_bwd, lib.sir_layer_norm_act_drop_bwd, drop,
+                        _ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(weight), _ptr(bias), _ptr(mean),
+                        _ptr(rstd), int(act), float(slope), _ptr(dX), _ld(dX, N), _ptr(part), _ptr(db_part), 2 * npad,
+                        _stream(X.device))
     _check(rc, lib)
     tot = col_sum(part[:parts])             # (the pad columns of an N % 4 != 0 row are summed and dropped)
-    return tot[:N], tot[npad:npad + N]
-
-
-def layer_norm_act_drop_fwd(X, weight, bias, eps, act, slope, R, Y, mean, rstd, drop):
-    """:func:`layer_norm_act_fwd` with the layer dropout between the activation and the add of R
-    (``sir_layer_norm_act_drop_fwd``); ``drop`` = (seed, p), the bits of an [M, N] block at col0 = 0."""
-    lib = load()
-    M, N = X.shape
-    with _Timed("sir_layer_norm_act_fwd", X.device):
-        rc = lib.sir_layer_norm_act_drop_fwd(_ptr(X), _ld(X, N), M, N, _ptr(weight), _ptr(bias), float(eps), int(act),
-                                             float(slope), _ptr(R), _ld(R, N) if R is not None else 0, _ptr(Y),
-                                             _ld(Y, N), _ptr(mean), _ptr(rstd), _drop(drop), _stream(X.device))
-    _check(rc, lib)
-
-
-def layer_norm_act_drop_bwd(X, dY, weight, bias, mean, rstd, act, slope, dX, drop):
-    """Backward of :func:`layer_norm_act_drop_fwd` (the same ``drop``); returns (dweight, dbias) as
-    :func:`layer_norm_act_bwd`."""
-    lib = load()
-    M, N = X.shape
-    parts = int(lib.sir_layer_norm_bwd_parts(M, N))
-    if parts < 0:
-        raise RuntimeError(f"sir_layer_norm_bwd_parts({M}, {N}): sizes out of range")
-    npad = (N + 3) // 4 * 4
-    part = torch.empty((max(parts, 1), 2 * npad), device=X.device, dtype=torch.float32)
-    db_part = part[:, npad:]
-    with _Timed("sir_layer_norm_act_bwd", X.device):
-        rc = lib.sir_layer_norm_act_drop_bwd(_ptr(X), _ld(X, N), _ptr(dY), _ld(dY, N), M, N, _ptr(weight), _ptr(bias),
-                                             _ptr(mean), _ptr(rstd), int(act), float(slope), _ptr(dX), _ld(dX, N),
-                                             _ptr(part), _ptr(db_part), 2 * npad, _drop(drop), _stream(X.device))
-    _check(rc, lib)
-    tot = col_sum(part[:parts])
     return tot[:N], tot[npad:npad + N]
 
 

@@ -81,10 +81,7 @@ class GraphNormActFunction(torch.autograd.Function):
         b = bias.contiguous().float() if bias is not None else None
         ms = mean_scale.contiguous().float() if mean_scale is not None else None
         Rc = R.contiguous() if R is not None else None
-        if drop is None:
-            _native.graph_norm_act_fwd(off, X, w, b, ms, eps, act, slope, Rc, Y, mean, std)
-        else:
-            _native.graph_norm_act_drop_fwd(off, X, w, b, ms, eps, act, slope, Rc, Y, mean, std, drop)
+        _native.graph_norm_act_fwd(off, X, w, b, ms, eps, act, slope, Rc, Y, mean, std, drop)
         ctx.save_for_backward(X, w, b if b is not None else w, ms if ms is not None else w, mean, std, off)
         ctx.has_b, ctx.has_ms, ctx.has_r = bias is not None, mean_scale is not None, R is not None
         ctx.act, ctx.slope, ctx.drop = act, slope, drop
@@ -98,12 +95,8 @@ class GraphNormActFunction(torch.autograd.Function):
         dY = dY.contiguous().float()
         dX = torch.empty_like(X)
         parts = torch.empty((3 if ms is not None else 2,) + tuple(mean.shape), device=X.device, dtype=torch.float32)
-        if ctx.drop is None:
-            _native.graph_norm_act_bwd(off, X, dY, w, b, ms, mean, std, ctx.act, ctx.slope, dX, parts[0],
-                                       parts[2] if ms is not None else None, parts[1])
-        else:
-            _native.graph_norm_act_drop_bwd(off, X, dY, w, b, ms, mean, std, ctx.act, ctx.slope, dX, parts[0],
-                                            parts[2] if ms is not None else None, parts[1], ctx.drop)
+        _native.graph_norm_act_bwd(off, X, dY, w, b, ms, mean, std, ctx.act, ctx.slope, dX, parts[0],
+                                   parts[2] if ms is not None else None, parts[1], ctx.drop)
         sums = parts.sum(1)
         return (dX, sums[0], sums[1] if ctx.has_b else None, sums[2] if ms is not None else None, None, None, None,
                 None, dY if ctx.has_r else None, None)
@@ -200,11 +193,9 @@ class BatchNormActFunction(torch.autograd.Function):
                                          _native.batch_norm_work(M, N, X.device))
         else:
             mean, invstd = running_mean.double(), torch.rsqrt(running_var.double() + eps)
-        if M > 0 and drop is None:
-            _native.batch_norm_act_fwd(X, mean, invstd, w, b, act, slope, _rows(R, N) if R is not None else None, Y)
-        elif M > 0:
-            _native.batch_norm_act_drop_fwd(X, mean, invstd, w, b, act, slope, _rows(R, N) if R is not None else None,
-                                            Y, drop)
+        if M > 0:
+            _native.batch_norm_act_fwd(X, mean, invstd, w, b, act, slope, _rows(R, N) if R is not None else None, Y,
+                                       drop)
         ctx.save_for_backward(X, w, b, mean, invstd)
         ctx.cfg = (bool(training), act, slope, R is not None)
         ctx.drop = drop
@@ -221,11 +212,7 @@ class BatchNormActFunction(torch.autograd.Function):
             dw = torch.empty((N,), device=X.device, dtype=torch.float32)
             db = torch.empty_like(dw)
             work = _native.batch_norm_work(M, N, X.device)
-            if ctx.drop is None:
-                _native.batch_norm_act_bwd(X, dY, mean, invstd, w, b, act, slope, training, dX, dw, db, work)
-            else:
-                _native.batch_norm_act_drop_bwd(X, dY, mean, invstd, w, b, act, slope, training, dX, dw, db, work,
-                                                ctx.drop)
+            _native.batch_norm_act_bwd(X, dY, mean, invstd, w, b, act, slope, training, dX, dw, db, work, ctx.drop)
         else:
             dw = torch.zeros((N,), device=X.device, dtype=torch.float32)
             db = torch.zeros_like(dw)
@@ -246,11 +233,9 @@ class LayerNormActFunction(torch.autograd.Function):
         Y = torch.empty((M, N), device=X.device, dtype=torch.float32)
         mean = torch.empty((M,), device=X.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-        if M > 0 and drop is None:
-            _native.layer_norm_act_fwd(X, w, b, eps, act, slope, _rows(R, N) if R is not None else None, Y, mean, rstd)
-        elif M > 0:
-            _native.layer_norm_act_drop_fwd(X, w, b, eps, act, slope, _rows(R, N) if R is not None else None, Y, mean,
-                                            rstd, drop)
+        if M > 0:
+            _native.layer_norm_act_fwd(X, w, b, eps, act, slope, _rows(R, N) if R is not None else None, Y, mean, rstd,
+                                       drop)
         ctx.save_for_backward(X, w, b, mean, rstd)
         ctx.cfg = (act, slope, R is not None)
         ctx.drop = drop
@@ -263,10 +248,7 @@ class LayerNormActFunction(torch.autograd.Function):
         M, N = X.shape
         dY = _rows(dY.float(), N)
         dX = torch.empty((M, N), device=X.device, dtype=torch.float32)
-        if ctx.drop is None:
-            dw, db = _native.layer_norm_act_bwd(X, dY, w, b, mean, rstd, act, slope, dX)
-        else:
-            dw, db = _native.layer_norm_act_drop_bwd(X, dY, w, b, mean, rstd, act, slope, dX, ctx.drop)
+        dw, db = _native.layer_norm_act_bwd(X, dY, w, b, mean, rstd, act, slope, dX, ctx.drop)
         return dX, dw, db, None, None, None, dY if has_r else None, None
 
 

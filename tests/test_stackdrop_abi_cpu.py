@@ -63,7 +63,10 @@ def test_symbols_and_version():
         # the sibling's argument list with one pointer (the sir_dropout_t*) before the stream
         res, args = _native.SIGNATURES[sibling]
         assert _native.SIGNATURES[name] == (res, args[:-1] + [ctypes.c_void_p] + args[-1:]), name
-        assert hasattr(_native, name[len("sir_"):])
+        # bound: the sibling's wrapper calls this entry when it is given the dropout, as its last parameter `drop`
+        wrapper = getattr(_native, sibling[len("sir_"):])
+        code = wrapper.__code__
+        assert code.co_varnames[code.co_argcount - 1] == "drop" and wrapper.__defaults__ == (None,), name
 
 
 def test_empty_work_is_a_no_op():

@@ -160,10 +160,20 @@ DROP_ENTRIES = ("batch_norm_act_drop_fwd", "batch_norm_act_drop_bwd", "layer_nor
 
 
 def _count_drop_entries(monkeypatch):
+    """Records ``<norm>_act_drop_fwd`` / ``_bwd`` for every call of a fused norm wrapper that is given a layer
+    dropout (``drop`` not None, last positional argument or keyword): the calls that take the C ``*_drop_*`` entries."""
     calls = []
     for name in DROP_ENTRIES:
-        orig = getattr(_native, name)
-        monkeypatch.setattr(_native, name, lambda *a, _o=orig, _n=name, **k: calls.append(_n) or _o(*a, **k))
+        wrapper = name.replace("_drop", "")
+        orig = getattr(_native, wrapper)
+        n_plain = orig.__code__.co_argcount - 1             # ``drop`` is the last parameter
+
+        def spy(*a, _o=orig, _n=name, _k=n_plain, **k):
+            drop = k["drop"] if "drop" in k else (a[_k] if len(a) > _k else None)
+            if drop is not None:
+                calls.append(_n)
+            return _o(*a, **k)
+        monkeypatch.setattr(_native, wrapper, spy)
     return calls
 
 
@@ -219,8 +229,8 @@ def test_bad_probabilities_are_refused():
             case.fa(case.mod, case.X, None, dropout=(SEED, p))
     Y, mean = torch.empty_like(case.X), torch.empty(5, device=DEV)
     with pytest.raises(RuntimeError, match="sir_layer_norm_act_drop_fwd: dropout p is NaN"):
-        _native.layer_norm_act_drop_fwd(case.X, case.mod.weight.detach(), case.mod.bias.detach(), 1e-5, 1, 0.0, None,
-                                        Y, mean, torch.empty_like(mean), (SEED, float("nan")))
+        _native.layer_norm_act_fwd(case.X, case.mod.weight.detach(), case.mod.bias.detach(), 1e-5, 1, 0.0, None,
+                                   Y, mean, torch.empty_like(mean), drop=(SEED, float("nan")))
 
 
 # ------------------------------------------------------------------ seeds

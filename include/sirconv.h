@@ -28,7 +28,8 @@
  *  - the graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling, dgl.broadcast_nodes; ogbg-molhiv/model.py:69,85,
  *    zinc/model.py:41): sir_graph_pool_fwd / _bwd (sir_graph_pool_work_floats, sir_graph_pool_slab_rows);
  *  - Correct & Smooth's label propagation (ogbn-arxiv/correct_and_smooth.py:41-58): sir_label_prop_step;
- *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm.
+ *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm, and the per-layer
+ *    DropEdge (models/utils.py:96-102) derived from a built plan: sir_plan_drop_edges.
  *
  * Conventions
  *  - All pointers are DEVICE pointers; all work is enqueued on `stream` (a hipStream_t,
@@ -725,6 +726,41 @@ int sir_csr_build(const int64_t* rows, const int64_t* cols, int64_t E, int64_t n
  * dst-CSR map of the sign-mask backward. */
 int sir_csr_perm(const int64_t* eid_a, const int64_t* eid_b, int64_t E, int32_t* pos_ws, int32_t* perm,
                  void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DropEdge (dgl.transforms.DropEdge, the reference's per-layer edge dropout, models/utils.py:96-102): the
+ * dropped graph's COMPLETE plan derived from the parent's two CSRs without a sort.  Added under ABI 17 (new
+ * symbols only).  A dropped graph's row CSRs are order-preserving subsequences of the parent's, so the child
+ * is a flag, one prefix sum and a compaction per edge position, then the builder's own plan stage.
+ *
+ * Parent (device): the dst CSR dst_rowptr int32 [n_dst_rows+1], dst_col int32 [E], dst_eid int64 [E]; the
+ * src CSR likewise plus src_perm int32 [E] (sir_csr_perm's map); `chunk` the plan's chunk.
+ * Exactly one keep source, indexed by parent EDGE ID:
+ *   keep : uint8 [E], non-zero = keep;
+ *   drop : edge e is kept iff the hash of sir_dropout_t keeps element (e, 0) — the bit sir_dropout_apply
+ *          gives row e of an [E, 1] block at col0 = 0.  p <= 0 keeps everything, p >= 1 nothing, a NaN p is
+ *          SIR_EINVAL; seed_ptr as in sir_dropout_t.
+ * Outputs (device): what sir_csr_build / sir_csr_perm return for the compacted COO (src[keep], dst[keep]),
+ * bit for bit — dgl.remove_edges semantics: survivors renumbered 0..E'-1 in ascending parent id, rows keep
+ * ascending edge id:
+ *   out_dst_rowptr / out_src_rowptr int32 [n_rows+1]; out_*_col int32 [E], out_*_eid int64 [E] (new ids),
+ *   out_src_perm int32 [E], kept int64 [E] (the survivors' parent ids, ascending): capacity E, E' used;
+ *   out_*_items / out_*_splits: sir_csr_build's capacities for the PARENT E;
+ *   counts int64 [9] = {n_items, n_splits, n_slots, max_degree} of the dst CSR, the same of the src CSR, E'.
+ * workspace: sir_plan_drop_workspace(n_dst_rows, n_src_rows, E) bytes (-1: sizes out of range).
+ * Integer arithmetic only, deterministic, no host synchronisation; the caller reads `counts` to size the
+ * views.  E < 2^31, chunk >= 1; E = 0, no rows, keep-all and keep-none are valid.
+ * ------------------------------------------------------------------------------------------- */
+int64_t sir_plan_drop_workspace(int64_t n_dst_rows, int64_t n_src_rows, int64_t E);
+
+int sir_plan_drop_edges(const int32_t* dst_rowptr, const int32_t* dst_col, const int64_t* dst_eid,
+                        const int32_t* src_rowptr, const int32_t* src_col, const int64_t* src_eid,
+                        const int32_t* src_perm, int64_t E, int64_t n_dst_rows, int64_t n_src_rows, int64_t chunk,
+                        const uint8_t* keep, const sir_dropout_t* drop,
+                        int32_t* out_dst_rowptr, int32_t* out_dst_col, int64_t* out_dst_eid, int32_t* out_dst_items,
+                        int32_t* out_dst_splits, int32_t* out_src_rowptr, int32_t* out_src_col, int64_t* out_src_eid,
+                        int32_t* out_src_items, int32_t* out_src_splits, int32_t* out_src_perm, int64_t* kept,
+                        int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Projection GEMMs of the layer: the nn.Linear calls conv.py:60-61 (Q, K), conv.py:65 (W_R) and

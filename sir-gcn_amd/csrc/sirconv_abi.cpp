@@ -1208,6 +1208,59 @@ int sir_csr_perm(const int64_t* eid_a, const int64_t* eid_b, int64_t E, int32_t*
     return finish(fn, sir::run_csr_perm(eid_a, eid_b, E, pos_ws, perm, static_cast<hipStream_t>(stream)), nullptr);
 }
 
+// ------------------------------------------------------------------------------ DropEdge plan derivation
+int64_t sir_plan_drop_workspace(int64_t n_dst_rows, int64_t n_src_rows, int64_t E) {
+    if (n_dst_rows < 0 || n_src_rows < 0 || E < 0 || E >= INT32_MAX || n_dst_rows >= INT32_MAX ||
+        n_src_rows >= INT32_MAX)
+        return -1;
+    return sir::plan_drop_workspace(n_dst_rows, n_src_rows, E);
+}
+
+int sir_plan_drop_edges(const int32_t* dst_rowptr, const int32_t* dst_col, const int64_t* dst_eid,
+                        const int32_t* src_rowptr, const int32_t* src_col, const int64_t* src_eid,
+                        const int32_t* src_perm, int64_t E, int64_t n_dst_rows, int64_t n_src_rows, int64_t chunk,
+                        const uint8_t* keep, const sir_dropout_t* drop,
+                        int32_t* out_dst_rowptr, int32_t* out_dst_col, int64_t* out_dst_eid, int32_t* out_dst_items,
+                        int32_t* out_dst_splits, int32_t* out_src_rowptr, int32_t* out_src_col, int64_t* out_src_eid,
+                        int32_t* out_src_items, int32_t* out_src_splits, int32_t* out_src_perm, int64_t* kept,
+                        int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "sir_plan_drop_edges";
+    if (E < 0 || n_dst_rows < 0 || n_src_rows < 0) return fail(SIR_EINVAL, fn, "negative size");
+    if (E >= INT32_MAX || n_dst_rows >= INT32_MAX || n_src_rows >= INT32_MAX)
+        return fail(SIR_EINVAL, fn, "int32 plan: E and the row counts must be < 2^31");
+    if (chunk < 1 || chunk > (1 << 24)) return fail(SIR_EINVAL, fn, "chunk must be in [1, 2^24]");
+    if ((keep != nullptr) == (drop != nullptr))
+        return fail(SIR_EINVAL, fn, "exactly one keep source: the `keep` mask or `drop`");
+    if (drop != nullptr && drop->p != drop->p) return fail(SIR_EINVAL, fn, "dropout p is NaN");
+    if (E > 0 && (n_dst_rows == 0 || n_src_rows == 0)) return fail(SIR_EINVAL, fn, "edges need rows on both sides");
+    if (out_dst_rowptr == nullptr || out_src_rowptr == nullptr || counts == nullptr)
+        return fail(SIR_EINVAL, fn, "NULL output rowptr/counts");
+    if (E > 0 && (dst_rowptr == nullptr || dst_col == nullptr || dst_eid == nullptr || src_rowptr == nullptr ||
+                  src_col == nullptr || src_eid == nullptr || src_perm == nullptr))
+        return fail(SIR_EINVAL, fn, "NULL parent CSR buffer");
+    if (E > 0 && (out_dst_col == nullptr || out_dst_eid == nullptr || out_src_col == nullptr ||
+                  out_src_eid == nullptr || out_src_perm == nullptr || kept == nullptr))
+        return fail(SIR_EINVAL, fn, "NULL output edge buffer");
+    if ((n_dst_rows > 0 && (out_dst_items == nullptr || out_dst_splits == nullptr)) ||
+        (n_src_rows > 0 && (out_src_items == nullptr || out_src_splits == nullptr)))
+        return fail(SIR_EINVAL, fn, "NULL items/splits");
+    const int64_t need = sir::plan_drop_workspace(n_dst_rows, n_src_rows, E);
+    if (workspace == nullptr || workspace_bytes < need) return fail(SIR_EINVAL, fn, "workspace too small");
+    sir::PlanDropArgs a{};
+    a.rowptr_d = dst_rowptr; a.col_d = dst_col; a.eid_d = dst_eid;
+    a.rowptr_s = src_rowptr; a.col_s = src_col; a.eid_s = src_eid; a.perm_s = src_perm;
+    a.E = E; a.n_dst_rows = n_dst_rows; a.n_src_rows = n_src_rows; a.chunk = (int)chunk;
+    a.keep = keep;
+    a.drop = to_drop(drop, 0);
+    a.rowptr_d2 = out_dst_rowptr; a.col_d2 = out_dst_col; a.eid_d2 = out_dst_eid; a.items_d2 = out_dst_items;
+    a.splits_d2 = out_dst_splits;
+    a.rowptr_s2 = out_src_rowptr; a.col_s2 = out_src_col; a.eid_s2 = out_src_eid; a.items_s2 = out_src_items;
+    a.splits_s2 = out_src_splits; a.perm_s2 = out_src_perm;
+    a.kept = kept; a.counts = counts;
+    return finish(fn, sir::run_plan_drop(a, workspace, workspace_bytes, static_cast<hipStream_t>(stream)),
+                  "the scans need more scratch than sir_plan_drop_workspace reserves");
+}
+
 int64_t sir_gemm_pack_bytes(int64_t N, int64_t K) {
     if (N <= 0 || K <= 0 || N > 65536 || K > 65536) return 0;
     return sir::gemm_pack_bytes(N, K);

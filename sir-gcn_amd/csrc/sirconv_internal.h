@@ -167,6 +167,31 @@ hipError_t run_csr_build(const int64_t* rows, const int64_t* cols, int64_t E, in
                          int64_t* counts, void* ws, int64_t ws_bytes, hipStream_t st);
 hipError_t run_csr_perm(const int64_t* eid_a, const int64_t* eid_b, int64_t E, int* pos_ws, int* perm,
                         hipStream_t st);
+// the plan stage of the builder (sirconv_plan.hip), shared with the DropEdge derivation: row degrees ->
+// rowptr, items, splits, counts[0..3].  acc_ws / off_ws: plan_rows_acc_bytes(n_rows) each; temp:
+// plan_rows_temp_bytes.  n_rows > 0; the caller zeroes counts.
+size_t plan_rows_acc_bytes(int64_t n_rows);
+hipError_t plan_rows_temp_bytes(int64_t n_rows, size_t* bytes);
+hipError_t run_plan_rows(const int* deg, int64_t n_rows, int chunk, void* acc_ws, void* off_ws, void* temp,
+                         size_t temp_bytes, int* rowptr, int32_t* items, int32_t* splits, int64_t* counts,
+                         hipStream_t st);
+
+// DropEdge: the child graph's plan from the parent's two CSRs (sirconv_dropedge.hip); the fields are
+// sir_plan_drop_edges'
+struct PlanDropArgs {
+    const int* rowptr_d; const int* col_d; const int64_t* eid_d;
+    const int* rowptr_s; const int* col_s; const int64_t* eid_s; const int* perm_s;
+    int64_t E, n_dst_rows, n_src_rows;
+    int chunk;
+    const uint8_t* keep;
+    Drop drop;                   // used when keep == nullptr
+    int* rowptr_d2; int* col_d2; int64_t* eid_d2; int32_t* items_d2; int32_t* splits_d2;
+    int* rowptr_s2; int* col_s2; int64_t* eid_s2; int32_t* items_s2; int32_t* splits_s2; int* perm_s2;
+    int64_t* kept;
+    int64_t* counts;
+};
+int64_t plan_drop_workspace(int64_t n_dst_rows, int64_t n_src_rows, int64_t E);
+hipError_t run_plan_drop(const PlanDropArgs& a, void* ws, int64_t ws_bytes, hipStream_t st);
 
 // per-edge dense layer fused with the gather and the reduce, sirconv_edgemlp.hip
 struct EdgeMlpArgs {

@@ -122,16 +122,12 @@ hipError_t layout(int64_t n_rows, int64_t E, Layout& L) {
                                                             key_bits(n_rows));
         if (err != hipSuccess) return err;
     }
-    if (n_rows > 0) {
-        hipError_t err = hipcub::DeviceScan::ExclusiveScan(nullptr, scan_bytes, (const RowAcc*)nullptr,
-                                                           (RowAcc*)nullptr, RowAdd(), RowAcc{0, 0, 0, 0},
-                                                           (int)n_rows);
-        if (err != hipSuccess) return err;
-    }
+    hipError_t serr = plan_rows_temp_bytes(n_rows, &scan_bytes);
+    if (serr != hipSuccess) return serr;
     size_t o = 0;
     L.deg = o;  o += up256(sizeof(int) * (size_t)(n_rows + 1));
-    L.acc = o;  o += up256(sizeof(RowAcc) * (size_t)(n_rows + 1));
-    L.off = o;  o += up256(sizeof(RowAcc) * (size_t)(n_rows + 1));
+    L.acc = o;  o += plan_rows_acc_bytes(n_rows);
+    L.off = o;  o += plan_rows_acc_bytes(n_rows);
     L.kin = o;  o += up256(sizeof(int) * (size_t)(E + 1));
     L.kout = o; o += up256(sizeof(int) * (size_t)(E + 1));
     L.vin = o;  o += up256(sizeof(int) * (size_t)(E + 1));
@@ -146,6 +142,33 @@ hipError_t layout(int64_t n_rows, int64_t E, Layout& L) {
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
+
+// The plan stage shared by the builder above and the DropEdge derivation (sirconv_dropedge.hip): per-row
+// degrees -> rowptr, work items, split rows and counts[0..3] (counts zeroed by the caller; n_rows > 0).
+size_t plan_rows_acc_bytes(int64_t n_rows) { return up256(sizeof(RowAcc) * (size_t)(n_rows + 1)); }
+
+hipError_t plan_rows_temp_bytes(int64_t n_rows, size_t* bytes) {
+    *bytes = 0;
+    if (n_rows <= 0) return hipSuccess;
+    return hipcub::DeviceScan::ExclusiveScan(nullptr, *bytes, (const RowAcc*)nullptr, (RowAcc*)nullptr, RowAdd(),
+                                             RowAcc{0, 0, 0, 0}, (int)n_rows);
+}
+
+hipError_t run_plan_rows(const int* deg, int64_t n_rows, int chunk, void* acc_ws, void* off_ws, void* temp,
+                         size_t temp_bytes, int* rowptr, int32_t* items, int32_t* splits, int64_t* counts,
+                         hipStream_t st) {
+    RowAcc* acc = static_cast<RowAcc*>(acc_ws);
+    RowAcc* off = static_cast<RowAcc*>(off_ws);
+    hipLaunchKernelGGL(k_row_acc, dim3(nblk(n_rows)), dim3(256), 0, st, deg, n_rows, chunk, acc);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    size_t tb = temp_bytes;
+    err = hipcub::DeviceScan::ExclusiveScan(temp, tb, acc, off, RowAdd(), RowAcc{0, 0, 0, 0}, (int)n_rows, st);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_rows, dim3(nblk(n_rows)), dim3(256), 0, st, acc, off, n_rows, chunk, rowptr,
+                       reinterpret_cast<int4*>(items), reinterpret_cast<int4*>(splits), counts);
+    return hipGetLastError();
+}
 
 int64_t csr_build_workspace(int64_t n_rows, int64_t E) {
     Layout L;
@@ -183,14 +206,7 @@ hipError_t run_csr_build(const int64_t* rows, const int64_t* cols, int64_t E, in
         hipLaunchKernelGGL(k_gather, dim3(nblk(E)), dim3(256), 0, st, vout, cols, E, n_cols, col, eid);
         if ((err = hipGetLastError()) != hipSuccess) return err;
     }
-    hipLaunchKernelGGL(k_row_acc, dim3(nblk(n_rows)), dim3(256), 0, st, deg, n_rows, chunk, acc);
-    if ((err = hipGetLastError()) != hipSuccess) return err;
-    size_t tb = L.temp_bytes;
-    err = hipcub::DeviceScan::ExclusiveScan(temp, tb, acc, off, RowAdd(), RowAcc{0, 0, 0, 0}, (int)n_rows, st);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_rows, dim3(nblk(n_rows)), dim3(256), 0, st, acc, off, n_rows, chunk, rowptr,
-                       reinterpret_cast<int4*>(items), reinterpret_cast<int4*>(splits), counts);
-    return hipGetLastError();
+    return run_plan_rows(deg, n_rows, chunk, acc, off, temp, L.temp_bytes, rowptr, items, splits, counts, st);
 }
 
 hipError_t run_csr_perm(const int64_t* eid_a, const int64_t* eid_b, int64_t E, int* pos_ws, int* perm,

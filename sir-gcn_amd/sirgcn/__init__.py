@@ -9,8 +9,9 @@ from .norm import GraphNorm, GraphBatchNorm, GraphLayerNorm, GetNorm  # noqa: F4
 from .econv import SIREConv  # noqa: F401
 from .readout import SumPooling, AvgPooling, MaxPooling, readout_nodes, broadcast_nodes  # noqa: F401
 from .propagate import label_spreading, correct_and_smooth, Clamp, FixRows  # noqa: F401
+from .dropedge import DropEdge, drop_edges, drop_edge_keep  # noqa: F401
 from . import _native  # noqa: F401
 
-__all__ = ["label_spreading", "correct_and_smooth", "Clamp", "FixRows",
+__all__ = ["DropEdge", "drop_edges", "drop_edge_keep", "label_spreading", "correct_and_smooth", "Clamp", "FixRows",
 "SIRConv", "SIREConv", "GraphNorm", "GraphBatchNorm", "GraphLayerNorm", "GetNorm", "Graph", "GraphPlan", "RowCSR", "EdgeAggregate", "batch", "get_plan",
            "build_row_csr", "SumPooling", "AvgPooling", "MaxPooling", "readout_nodes", "broadcast_nodes"]

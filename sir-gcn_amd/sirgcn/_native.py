@@ -78,6 +78,9 @@ SIGNATURES = {
     "sir_csr_build_workspace": (ctypes.c_int64, [_I64, _I64]),
     "sir_csr_build": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "sir_csr_perm": (ctypes.c_int, [_P, _P, _I64, _P, _P, _P]),
+    "sir_plan_drop_workspace": (ctypes.c_int64, [_I64, _I64, _I64]),
+    "sir_plan_drop_edges": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "sir_gemm_pack_bytes": (ctypes.c_int64, [_I64, _I64]),
     "sir_gemm_pack": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _P, _P]),
     "sir_gemm_nt": (ctypes.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P]),
@@ -509,6 +512,48 @@ def csr_perm(eid_a, eid_b):
     rc = lib.sir_csr_perm(_ptr(eid_a), _ptr(eid_b), E, _ptr(pos), _ptr(perm), _stream(eid_a.device))
     _check(rc, lib)
     return perm
+
+
+def plan_drop_edges(dst, src, chunk, keep=None, drop=None):
+    """The dropped graph's plan from the parent's two CSRs (``sir_plan_drop_edges``, async).  ``dst`` / ``src``:
+    the parent's RowCSRs (``src.perm`` set); exactly one of ``keep`` (uint8 [E] by edge id) and ``drop`` =
+    (seed, p).  Returns (dst parts, src parts, perm, kept, counts): each parts tuple is (rowptr, col, eid,
+    items_cap, splits_cap) with col / eid / perm / kept at the parent's E (E' used) and ``counts`` = int64 [9]
+    {n_items, n_splits, n_slots, max_degree} x {dst, src}, E' on the device."""
+    lib = load()
+    dev = dst.rowptr.device
+    E = dst.col.numel()
+    n_d, n_s = dst.n_rows, src.n_rows
+    if (keep is None) == (drop is None):
+        raise ValueError("plan_drop_edges: exactly one of keep and drop")
+    if keep is not None and not (keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == E
+                                 and keep.device == dev):
+        raise RuntimeError("plan_drop_edges: keep must be a contiguous uint8 [E] tensor on the plan's device")
+    if keep is not None and E == 0:                 # an empty tensor has no address; the entry needs one source
+        keep = torch.zeros((1,), dtype=torch.uint8, device=dev)
+    ws_bytes = lib.sir_plan_drop_workspace(n_d, n_s, E)
+    if ws_bytes < 0:
+        raise RuntimeError("sir_plan_drop_workspace failed (sizes out of range or no device)")
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+
+    def parts(n):
+        return (torch.empty((n + 1,), dtype=torch.int32, device=dev),
+                torch.empty((E,), dtype=torch.int32, device=dev),
+                torch.empty((E,), dtype=torch.int64, device=dev),
+                torch.empty((n + E // chunk + 1, 4), dtype=torch.int32, device=dev),
+                torch.empty((min(n, E // (chunk + 1)) + 1, 4), dtype=torch.int32, device=dev))
+
+    d, s = parts(n_d), parts(n_s)
+    perm = torch.empty((E,), dtype=torch.int32, device=dev)
+    kept = torch.empty((E,), dtype=torch.int64, device=dev)
+    counts = torch.empty((9,), dtype=torch.int64, device=dev)
+    with _Timed("sir_plan_drop_edges", dev):
+        rc = lib.sir_plan_drop_edges(_ptr(dst.rowptr), _ptr(dst.col), _ptr(dst.eid), _ptr(src.rowptr), _ptr(src.col),
+                                     _ptr(src.eid), _ptr(src.perm), E, n_d, n_s, chunk, _ptr(keep), _drop(drop),
+                                     *(_ptr(t) for t in d), *(_ptr(t) for t in s), _ptr(perm), _ptr(kept),
+                                     _ptr(counts), _ptr(ws), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return d, s, perm, kept, counts
 
 
 # ------------------------------------------------------------------------------ GraphNorm

@@ -246,6 +246,21 @@ class GraphPlan:
         self.out_deg = (self.src.rowptr[1:] - self.src.rowptr[:-1]).to(torch.int64)
         self._norms = {}
 
+    @classmethod
+    def from_parts(cls, dst, src, num_nodes, device):
+        """A plan from two finished :class:`RowCSR` (``src.perm`` set), e.g. the ones ``sirgcn.drop_edges``
+        derives from a parent plan: nothing is built; the degrees and the lazily computed norms come from
+        the given ``rowptr``."""
+        self = cls.__new__(cls)
+        self.num_nodes = int(num_nodes)
+        self.device = torch.device(device)
+        self.num_edges = int(dst.col.numel())
+        self.dst, self.src = dst, src
+        self.in_deg = (dst.rowptr[1:] - dst.rowptr[:-1]).to(torch.int64)
+        self.out_deg = (src.rowptr[1:] - src.rowptr[:-1]).to(torch.int64)
+        self._norms = {}
+        return self
+
     def norms(self, agg):
         """``conv.py:51-57``: fp32 deg^-1/2 for ``sym`` (clamp(min=1)), else None (== ones)."""
         if agg != "sym":
@@ -273,16 +288,23 @@ class GraphPlan:
 _weak_plans = weakref.WeakKeyDictionary()
 
 
-def get_plan(graph, device, chunk=DEFAULT_CHUNK):
-    """Return the cached :class:`GraphPlan` of ``graph`` on ``device`` (build on first use)."""
-    device = torch.device(device)
-    key = (str(device), chunk)
+def plan_cache(graph):
+    """The per-graph cache dict :func:`get_plan` keeps its plans in (a throw-away dict for an object that
+    can hold neither an attribute nor a weak reference)."""
     cache = getattr(graph, "_plans", None)
     if cache is None:
         try:
             cache = _weak_plans.setdefault(graph, {})
         except TypeError:
             cache = {}
+    return cache
+
+
+def get_plan(graph, device, chunk=DEFAULT_CHUNK):
+    """Return the cached :class:`GraphPlan` of ``graph`` on ``device`` (build on first use)."""
+    device = torch.device(device)
+    key = (str(device), chunk)
+    cache = plan_cache(graph)
     plan = cache.get(key)
     if plan is not None:
         return plan

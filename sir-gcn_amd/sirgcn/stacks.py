@@ -21,11 +21,17 @@ MI355X modules (tests, ``bench.py --workload``):
 activation and before the residual add (``ogbn-arxiv/model.py:49,70``), after the activation in zinc order
 (``zinc/model.py:24,56``).  A norm whose ``forward_act`` takes ``dropout`` (this package's three) runs it inside
 its fused pass from a hashed mask that is never stored; otherwise the stack applies ``self.dropout`` itself.
+
+``edge_dropout`` is the graph-level models' DropEdge (``self.edge_drop`` of ``zinc/model.py:25,50-54``,
+``sbm-dataset/model.py:42``): every layer's conv runs on its own dropped graph — in eval mode too, as the
+reference's does — while the norm sees the original graph (``sirgcn.dropedge``).
 """
 import functools
 import inspect
 
 from torch import nn
+
+from .dropedge import DropEdge
 
 
 def _resid_act(y, resid, activation, order, r_link=None, out_link=None):
@@ -60,7 +66,7 @@ class SIRStack(nn.Module):
     link_residual_grads = True
 
     def __init__(self, conv_cls, hidden, num_layers, activation, agg_type="sum", order="arxiv",
-                 norm_cls=None, conv_activation=None, feat_dropout=0, dropout=0):
+                 norm_cls=None, conv_activation=None, feat_dropout=0, dropout=0, edge_dropout=0):
         super().__init__()
         if order not in ("arxiv", "zinc", "plain"):
             raise ValueError(order)
@@ -75,6 +81,9 @@ class SIRStack(nn.Module):
         # the layer dropout (the reference's attribute); fused into the norm pass when the norm offers it
         self.dropout = nn.Dropout(dropout)
         self.layer_seeds = None      # the layers' seed words of the last fused-dropout step (one per layer)
+        # DropEdge before every conv (a plain callable: no parameters, no state_dict entry); p = 0 hands the
+        # graph through untouched
+        self.edge_drop = DropEdge(edge_dropout)
 
     def forward(self, graph, feats):
         p_drop = self.dropout.p if self.training else 0
@@ -96,11 +105,12 @@ class SIRStack(nn.Module):
                     self.layer_seeds = seeds[len(drawing):].bitwise_or_(1 << 62)
         link = None          # the GradLink of feats when a fused residual pass produced it
         for i, conv in enumerate(self.convs):
+            graph_ = self.edge_drop(graph)       # the conv's graph; the norm below keeps the original
             if self.order == "plain":
-                feats = conv(graph, feats)
+                feats = conv(graph_, feats)
                 continue
             resid = feats
-            feats = conv(graph, feats)
+            feats = conv(graph_, feats)
             if self.norms is None and not p_drop > 0:
                 # + resid and the activation in one pass when the operands allow (sirgcn.resact);
                 # the residual gradient of each layer's input handed to the layer that produced it

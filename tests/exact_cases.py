@@ -200,9 +200,14 @@ def mlp_inputs(graph, H, F):
     return cached(("mlpin", graph, H, F), make)
 
 
-def seq_expected(graph, H, F, agg, dtype=torch.float64):
-    """S = agg_e ReLU(W ReLU(Q[v] + K[u]) + b) and its gradients, by oracle.reference_cpu_step with the
-    callable sigma, identity projections and W_R = I."""
+SEQ_ACT_MODULE = {"identity": torch.nn.Identity, "relu": torch.nn.ReLU, "leaky": lambda: torch.nn.LeakyReLU(SLOPE)}
+# (act1, act2) of the Sequential sigma beside the (relu, relu) of every SEQ_SHAPES case: each stays dyadic
+SEQ_ACT_PAIRS = (("identity", "relu"), ("identity", "identity"), ("leaky", "identity"), ("relu", "identity"))
+
+
+def seq_expected(graph, H, F, agg, dtype=torch.float64, act1="relu", act2="relu"):
+    """S = agg_e act2(W act1(Q[v] + K[u]) + b) (ReLU, ReLU by default; names of SEQ_ACT_MODULE) and its
+    gradients, by oracle.reference_cpu_step with the callable sigma, identity projections and W_R = I."""
     def make():
         src, dst, V = GRAPHS[graph]
         Q, K, W, b, G = (t.to(dtype) for t in mlp_inputs(graph, H, F))
@@ -210,13 +215,13 @@ def seq_expected(graph, H, F, agg, dtype=torch.float64):
         with torch.no_grad():
             lin.weight.copy_(W)
             lin.bias.copy_(b)
-        sigma = torch.nn.Sequential(torch.nn.ReLU(), lin, torch.nn.ReLU())
+        sigma = torch.nn.Sequential(SEQ_ACT_MODULE[act1](), lin, SEQ_ACT_MODULE[act2]())
         X, W_Q, b_Q, W_K = _identity_layer(Q, K, H)
         r = oracle.reference_cpu_step(src, dst, V, X, W_Q, b_Q, W_K, torch.eye(F, dtype=dtype),
                                       torch.zeros(F, dtype=dtype), G, agg, sigma)
         return {"S": r["Y"], "dQ": r["dX"][:, :H], "dK": r["dX"][:, H:], "dW": lin.weight.grad.clone(),
                 "db": lin.bias.grad.clone()}
-    return cached(("seq", graph, H, F, agg, dtype), make)
+    return cached(("seq", graph, H, F, agg, dtype, act1, act2), make)
 
 
 def max_messages(graph, H, O, act, dtype=torch.float64):

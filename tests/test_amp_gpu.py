@@ -26,7 +26,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DT = {"bf16": torch.bfloat16, "f16": torch.float16}
 U = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11}
-ACTS = {"relu": nn.ReLU(), "leaky": nn.LeakyReLU(0.2), "gelu": nn.GELU()}
+ACTS = {"relu": nn.ReLU(), "leaky": nn.LeakyReLU(0.2), "gelu": nn.GELU(), "identity": nn.Identity(),
+        "gelu_tanh": nn.GELU(approximate="tanh")}
 AMP_SLACK = 1.25     # allowed ratio to the reference AMP path's own error (both dominated by the same GEMMs)
 
 
@@ -244,13 +245,19 @@ def _max16_graph(seed, V=400, E=5000):
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("H,O,act", [(256, 256, "leaky"), (256, 40, "relu"), (512, 512, "leaky"), (64, 48, "relu"),
-                                     (128, 200, "leaky")])
+                                     (128, 200, "leaky"), (256, 256, "identity"), (64, 48, "identity"),
+                                     (256, 256, "gelu_tanh")])
 def test_max_forward_16bit_kernel_semantics(dt, H, O, act):
     """The 16-bit max forward (sir_edge_mlp_fwd_stream_st at H = 256, sir_edge_mlp_fwd_st per item otherwise)
     against its stated semantics in fp64 on the host: a = round_dt(act1(Q[v] + K[u]) in fp32) from the 16-bit
     rows, h = a round_dt(W)^T + round_dt(b), Y[v] = max_e h, arg = the first arg-max edge, empty rows 0 / -1.
     ReLU / LeakyReLU: a is bit-identical on both sides, so Y may differ only by the fp32 accumulation
-    (<= 1e-5 of sum |a| |w| + |b|) and arg only where the row's two best h are closer than that."""
+    (<= 1e-5 of sum |a| |w| + |b|) and arg only where the row's two best h are closer than that.  Identity: a =
+    round_dt(z), the same argument.  tanh-GELU: the host's fp32 a and the kernel's differ by the two tanhf's and
+    the rounding of the formula's six operations, an absolute error within 8 * 2^-24 |z| (the error of 1 + tanh is
+    absolute, of the order of an ulp of 1, and is scaled by z / 2); where a 16-bit rounding boundary lies inside
+    that interval the kernel's rounded a may be the neighbouring 16-bit number, so for those elements only the
+    bound grows by that one ulp times |w|.  The bound of the other activations is not widened."""
     from sirgcn import edgemlp
     from sirgcn.graph import get_plan
     src, dst, V, gen = _max16_graph(H + O)
@@ -268,11 +275,16 @@ def test_max_forward_16bit_kernel_semantics(dt, H, O, act):
     s_, d_ = src[order], dst[order]
     q, k = QK[:, :H].float().cpu(), QK[:, H:].float().cpu()
     z = q[d_] + k[s_]                                        # fp32, as the kernel
-    a32 = torch.relu(z) if act == "relu" else torch.nn.functional.leaky_relu(z, slope)
+    a32 = {"relu": torch.relu, "leaky": lambda t: torch.nn.functional.leaky_relu(t, slope), "identity": lambda t: t,
+           "gelu_tanh": lambda t: torch.nn.functional.gelu(t, approximate="tanh")}[act](z)
     a = a32.to(DT[dt]).double()
     Wr, br = W.cpu().to(DT[dt]).double(), b.cpu().to(DT[dt]).double()
     h = a @ Wr.t() + br                                      # [E, O] fp64
     bound = 1e-5 * (a.abs() @ Wr.abs().t() + br.abs())
+    if act == "gelu_tanh":          # one 16-bit ulp of a where its rounding is not decided by the fp32 formula
+        err = 8 * 2.0 ** -24 * z.abs()
+        ulp = ((a32 + err).to(DT[dt]).double() - (a32 - err).to(DT[dt]).double()).abs()
+        bound = bound + ulp @ Wr.abs().t()
     Yr = torch.zeros(V, O, dtype=torch.float64)
     Ar = torch.full((V, O), -1, dtype=torch.int64)
     gap = torch.full((V, O), float("inf"), dtype=torch.float64)

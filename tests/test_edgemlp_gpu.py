@@ -18,6 +18,9 @@ from sirgcn.graph import Graph
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+# the five activation codes of the library (tests/activation_cases.py names them for the oracle)
+ACT_MODULES = {"leaky": lambda: nn.LeakyReLU(0.2), "relu": nn.ReLU, "gelu": nn.GELU, "identity": nn.Identity,
+               "gelu_tanh": lambda: nn.GELU(approximate="tanh")}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -154,7 +157,7 @@ def test_seq_sigma_fused_vs_oracle(agg, H, Fo, chunk, monkeypatch):
 
 
 @pytest.mark.parametrize("chunk", [256, 64, 4])
-@pytest.mark.parametrize("act", ["leaky", "relu", "gelu"])
+@pytest.mark.parametrize("act", ["leaky", "relu", "gelu", "identity", "gelu_tanh"])
 @pytest.mark.parametrize("H,O", [(256, 40), (64, 64), (300, 24), (128, 256), (100, 200), (512, 512)])
 def test_max_fused_vs_oracle_first_wins(act, H, O, chunk, monkeypatch):
     """Fused forward for H, O <= 512 (roman-empire: H = O = 512, heterophilous-datasets/README.md:8)
@@ -171,7 +174,7 @@ def test_max_fused_vs_oracle_first_wins(act, H, O, chunk, monkeypatch):
     d = 32
     X, dY = torch.randn(V, d, generator=gen), torch.randn(V, O, generator=gen)
     torch.manual_seed(O)
-    mod = {"leaky": nn.LeakyReLU(0.2), "relu": nn.ReLU(), "gelu": nn.GELU()}[act]
+    mod = ACT_MODULES[act]()
     m = SIRConv(d, H, O, mod, 0, agg_type="max").to(DEV)
     m.chunk = chunk
     g = Graph(src, dst, V)
@@ -358,7 +361,7 @@ def _no_edge_buffers(monkeypatch):
 
 
 @pytest.mark.parametrize("chunk", [256, 64, 4])
-@pytest.mark.parametrize("act", ["leaky", "relu", "gelu"])
+@pytest.mark.parametrize("act", ["leaky", "relu", "gelu", "identity", "gelu_tanh"])
 @pytest.mark.parametrize("H,O", [(256, 256), (256, 40), (64, 64), (300, 24), (128, 256), (100, 200), (512, 256),
                                  (4, 1)])
 def test_max_routed_backward_vs_oracle_first_wins(act, H, O, chunk, monkeypatch):
@@ -374,7 +377,7 @@ def test_max_routed_backward_vs_oracle_first_wins(act, H, O, chunk, monkeypatch)
     d = 32
     X, dY = torch.randn(V, d, generator=gen), torch.randn(V, O, generator=gen)
     torch.manual_seed(O + 1)
-    mod = {"leaky": nn.LeakyReLU(0.2), "relu": nn.ReLU(), "gelu": nn.GELU()}[act]
+    mod = ACT_MODULES[act]()
     m = SIRConv(d, H, O, mod, 0, agg_type="max").to(DEV)
     m.chunk = chunk
     g = Graph(src, dst, V)
@@ -475,7 +478,8 @@ def test_max_dw_rows_matches_tn_gemm(H, O, chunk, monkeypatch):
 
 
 @pytest.mark.parametrize("dw_qk", [True, False])
-@pytest.mark.parametrize("act", [nn.LeakyReLU(0.2), nn.ReLU(), nn.GELU(), nn.LeakyReLU(-0.3)])
+@pytest.mark.parametrize("act", [nn.LeakyReLU(0.2), nn.ReLU(), nn.GELU(), nn.LeakyReLU(-0.3), nn.Identity(),
+                                 nn.GELU(approximate="tanh")])
 @pytest.mark.parametrize("chunk", [256, 4])
 def test_max_hybrid_backward_matches_materialised(act, chunk, dw_qk, monkeypatch):
     """The default max backward when it fits (A materialised for dW_R via sir_max_dw_rows, dQ / dK from the

@@ -92,6 +92,40 @@ def test_seq_sigma_inputs(H, F, graph, agg):
         _same(r32[k], r64[k], f"seq {graph} {agg} H={H} F={F} {k}")
 
 
+@pytest.mark.parametrize("act1,act2", xc.SEQ_ACT_PAIRS)
+@pytest.mark.parametrize("graph,agg", GRAPH_AGG)
+@pytest.mark.parametrize("H,F", xc.SEQ_SHAPES)
+def test_seq_sigma_inputs_other_activations(H, F, graph, agg, act1, act2):
+    """The (act1, act2) pairs of tests/test_activations_gpu.py::test_seq_sigma_kernels_exact_other_activations:
+    Identity keeps integers, LeakyReLU(0.25) makes quarters — every result is still an fp32 number."""
+    r32 = xc.seq_expected(graph, H, F, agg, torch.float32, act1, act2)
+    r64 = xc.seq_expected(graph, H, F, agg, act1=act1, act2=act2)
+    for k in r64:
+        _same(r32[k], r64[k], f"seq {act1}/{act2} {graph} {agg} H={H} F={F} {k}")
+
+
+def test_seq_expected_defaults_are_relu_relu():
+    """The optional act1 / act2 of xc.seq_expected leave the (ReLU, ReLU) values as they were."""
+    a = xc.seq_expected("A", 16, 16, "mean")
+    b = xc.seq_expected("A", 16, 16, "mean", act1="relu", act2="relu")
+    assert all(torch.equal(a[k], b[k]) for k in a)
+    assert not torch.equal(a["S"], xc.seq_expected("A", 16, 16, "mean", act1="identity", act2="relu")["S"])
+
+
+@pytest.mark.parametrize("graph,agg", GRAPH_AGG)
+def test_identity_edge_kernel_inputs(graph, agg):
+    """sigma = identity on the edge-kernel inputs, at the full width: sums of integers (mean / sym on graph A:
+    divided by powers of two), the same in fp32 and fp64, |S| <= 4 * 2 * 1024.  "identity" is not one of
+    xc.ACT_NAMES: that tuple also drives the sign-mask and sigma'(0) cases, which identity has none of."""
+    assert "identity" not in xc.ACT_NAMES
+    H = xc.WIDTH
+    r32 = xc.edge_expected(graph, H, agg, "identity", torch.float32)
+    r64 = xc.edge_expected(graph, H, agg, "identity")
+    for name, a, b in zip(("S", "dQ", "dK"), r32, r64):
+        _same(a, b, f"{graph} {agg} identity {name}")
+        assert b.abs().max() <= 8192
+
+
 @pytest.mark.parametrize("act", xc.ACT_NAMES)
 @pytest.mark.parametrize("graph", ["A", "B"])
 @pytest.mark.parametrize("H,O", xc.MAX_SHAPES)

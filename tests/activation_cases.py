@@ -14,8 +14,10 @@ SLOPE = {_native.ACT_LEAKY: 0.2}        # every other code ignores its slope
 # the codes without a sign-mask backward: sigma' needs z itself, so the backward recomputes it
 RECOMPUTE_CODES = tuple(c for c in CODES if c not in (_native.ACT_RELU, _native.ACT_LEAKY))
 
-EDGE_H = (3, 30, 4, 16, 60, 76, 128, 136, 256, 300, 512, 1024)      # 3, 30: the scalar path (fp32 only)
-EDGE_H_16BIT = (16, 128, 256, 300, 1024)
+# 3, 30, 70, 130: the scalar path (fp32 only) at 1, 2, 4 values per lane; every other width class once or more
+# (tests/width_cases.py)
+EDGE_H = (3, 30, 4, 16, 60, 76, 128, 136, 256, 300, 512, 1024, 24, 70, 130, 640)
+EDGE_H_16BIT = (16, 128, 256, 300, 1024, 24, 60, 640)
 EDGE_CHUNKS = (4, 256)
 AGGS = ("sum", "mean", "sym")
 

@@ -56,13 +56,43 @@ def _graph_b():
     return src[p].contiguous(), dst[p].contiguous(), 60
 
 
-EDGE_H = (4, 12, 32, 60, 76, 128, 136, 256, 512, 776, 1024)      # fp32, bf16, fp16
-EDGE_H_SCALAR = (1, 3, 7, 30)                                     # fp32 only: scalar path, no sign mask
-SIRE_H = (4, 32, 80, 128, 132, 256, 1024)
-SEQ_SHAPES = ((16, 16), (32, 48), (100, 140), (256, 256))
-MAX_SHAPES = ((64, 64), (100, 200), (256, 40), (256, 256), (512, 512))
-GRAPHS = {"A": _graph_a(), "B": _graph_b()}
-AGGS_OF = {"A": ("sum", "mean", "sym"), "B": ("sum",)}      # mean / sym are exact on graph A only
+LADDER_C = 66
+
+
+def _graph_c():
+    """A degree ladder (sum and max only): node v < 66 receives exactly v edges, from (5 v + 3 j + 1) mod 66,
+    j < v; node 66 + u sends exactly u edges, to 66 + (7 u + 5 j + 2) mod 66, j < u; nodes 132, 133 are
+    isolated.  In-degrees of nodes 0..65 and out-degrees of nodes 66..131 are exactly 0..65: every tail
+    length after 0..4 full chunks of 16 / 8 / 5 / 4 edges, two periods of the longest loop structure,
+    63 / 64 / 65 around chunk 64 and every split residue at chunk 4.  Edge ids shuffled.  V = 134, E = 4290."""
+    L = LADDER_C
+    v = torch.arange(L).repeat_interleave(torch.arange(L))
+    j = torch.cat([torch.arange(d) for d in range(L)])
+    src = torch.cat([(5 * v + 3 * j + 1) % L, L + v])
+    dst = torch.cat([v, L + (7 * v + 5 * j + 2) % L])
+    p = torch.randperm(src.numel(), generator=torch.Generator().manual_seed(606))
+    return src[p].contiguous(), dst[p].contiguous(), 2 * L + 2
+
+
+# the widths of a list take every kernel shape the dispatchers can pick at its lowest legal width, at its highest
+# and in between (tests/width_cases.py holds the lists to that; tests/test_width_classes_cpu.py checks it)
+EDGE_H = (4, 12, 32, 60, 76, 128, 136, 256, 512, 776, 1024,       # fp32, bf16, fp16
+          16, 20, 36, 64, 68, 132, 260, 516, 640, 768, 772, 24, 300)
+EDGE_H_SCALAR = (1, 3, 7, 30, 63, 65, 99, 127, 129, 191, 193, 255)    # fp32 only: scalar path, no sign mask
+EDGE_H_UNALIGNED = (64, 128, 256)   # fp32, H % 4 == 0 rows behind an odd leading dimension: the scalar path, full
+SIRE_H = (4, 32, 80, 128, 132, 256, 1024, 16, 20, 36, 64, 68, 260, 512, 516, 640, 768, 772,
+          12, 24, 48, 200, 300, 776)
+SEQ_SHAPES = ((16, 16), (32, 48), (100, 140), (256, 256), (32, 100), (200, 128))
+MAX_SHAPES = ((64, 64), (100, 200), (256, 40), (256, 256), (512, 512), (32, 100), (64, 300), (200, 300))
+HELPER_F = (3, 64, 300, 70, 127, 129, 190, 253, 516, 768, 1024, 1, 4, 63, 65, 255, 256, 260, 512)
+GRAPHS = {"A": _graph_a(), "B": _graph_b(), "C": _graph_c()}
+# mean / sym are exact on graph A only
+AGGS_OF = {"A": ("sum", "mean", "sym"), "B": ("sum",), "C": ("sum",)}
+GRAPH_AGG = [(g, a) for g in GRAPHS for a in AGGS_OF[g]]
+
+
+def graphs_of(agg):
+    return [g for g in GRAPHS if agg in AGGS_OF[g]]
 _CACHE = {}
 
 

@@ -78,7 +78,8 @@ def _sweep_reference(H, agg, code):
 @pytest.mark.parametrize("H", ac.EDGE_H)
 def test_edge_kernels_other_activations_vs_oracle(H, agg, code, chunk):
     """sir_edge_agg_fwd / _bwd_dst / _bwd_src with sigma = Identity, erf-GELU, tanh-GELU at every width class —
-    the scalar path (3, 30), the sub-wave rows (4 .. 128), one to four full-wave passes (136 .. 1024) — on the
+    the scalar path at one, two and four values per lane (3, 30, 70, 130), the sub-wave rows (4 .. 128), one to four
+    full-wave passes (136 .. 1024, 640 with three vectors per lane; tests/width_cases.py) — on the
     width sweep's graph with split rows in both CSRs (chunk 4) and in the dst CSR (chunk 256): S, dQ, dK against
     the fp32 / fp64 oracle at 1e-5.  These codes have no sign mask, so the backward is the recompute one (with
     the Gm hand-off for mean).  The erf and tanh formulas lie >= 5e-5 apart on these inputs
@@ -173,9 +174,7 @@ def test_identity_edge_kernels_exact(dt, H, agg):
     dtype = DT[dt]
     code = _native.ACT_IDENTITY
     assert _native.mask_words(H, code) == 0
-    for graph in ("A", "B"):
-        if agg not in xc.AGGS_OF[graph]:
-            continue
+    for graph in xc.graphs_of(agg):
         Q, K, G, _ = (t.to(DEV, dtype) for t in xc.edge_inputs(graph, H))
         wS, wdQ, wdK = (t.float().to(dtype).to(DEV) for t in xc.edge_expected(graph, H, agg, "identity"))
         for chunk in (4, 64, 256):
@@ -356,7 +355,7 @@ def test_seq_sigma_other_activations_under_bf16_autocast(a1, a2):
 # ----------------------------------------------------------------------------- (d) exact integers, MLP kernels
 SEQ_CODE = {"identity": (_native.ACT_IDENTITY, 0.0), "relu": (_native.ACT_RELU, 0.0),
             "leaky": (_native.ACT_LEAKY, xc.SLOPE)}
-GRAPH_AGG = [(g, a) for g in ("A", "B") for a in xc.AGGS_OF[g]]
+GRAPH_AGG = xc.GRAPH_AGG
 
 
 @pytest.mark.parametrize("a1,a2", xc.SEQ_ACT_PAIRS, ids=[f"{a}-{b}" for a, b in xc.SEQ_ACT_PAIRS])

@@ -17,6 +17,7 @@ from torch import nn
 
 import oracle
 from conftest import golden_manifest, load_case, rel_err
+import width_cases as wc
 
 from sirgcn import _native, linalg
 from sirgcn.conv import EdgeAggregate, SIRConv, activation_code
@@ -244,9 +245,7 @@ def _max16_graph(seed, V=400, E=5000):
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-@pytest.mark.parametrize("H,O,act", [(256, 256, "leaky"), (256, 40, "relu"), (512, 512, "leaky"), (64, 48, "relu"),
-                                     (128, 200, "leaky"), (256, 256, "identity"), (64, 48, "identity"),
-                                     (256, 256, "gelu_tanh")])
+@pytest.mark.parametrize("H,O,act", wc.MAX16_SHAPES)
 def test_max_forward_16bit_kernel_semantics(dt, H, O, act):
     """The 16-bit max forward (sir_edge_mlp_fwd_stream_st at H = 256, sir_edge_mlp_fwd_st per item otherwise)
     against its stated semantics in fp64 on the host: a = round_dt(act1(Q[v] + K[u]) in fp32) from the 16-bit

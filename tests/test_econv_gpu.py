@@ -12,6 +12,7 @@ from torch import nn
 
 import oracle
 from conftest import assert_close, assert_parity
+import width_cases as wc
 from exact_cases import encode_mask as _encode_mask
 
 from sirgcn import SIREConv, _native
@@ -22,7 +23,7 @@ from sirgcn.graph import Graph, GraphPlan
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 V, NE = 67, 700
-HS = [4, 32, 80, 128, 132, 256, 300, 512, 1024]
+HS = wc.ECONV_HS
 AGGS = ["sum", "mean", "sym"]
 ACTS = {"relu": (nn.ReLU(), _native.ACT_RELU, 0.0), "leaky": (nn.LeakyReLU(0.2), _native.ACT_LEAKY, 0.2)}
 

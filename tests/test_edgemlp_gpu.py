@@ -12,6 +12,7 @@ from torch import nn
 
 import oracle
 from conftest import assert_parity, tie_conditioned
+import width_cases as wc
 
 from sirgcn import SIRConv, _native
 from sirgcn.graph import Graph
@@ -128,7 +129,7 @@ def _no_generic(monkeypatch):
 
 @pytest.mark.parametrize("chunk", [256, 4])
 @pytest.mark.parametrize("agg", ["sum", "mean", "sym"])
-@pytest.mark.parametrize("H,Fo", [(64, 64), (32, 48), (16, 16), (200, 200), (128, 96), (100, 140), (256, 256)])
+@pytest.mark.parametrize("H,Fo", wc.SEQ_PARITY_SHAPES)
 def test_seq_sigma_fused_vs_oracle(agg, H, Fo, chunk, monkeypatch):
     """H, F up to 256 (the DictionaryLookup sweep's nhidden = 4n reaches 200 at n = 50,
     dictionary-lookup/README.md:8) on the fused kernels — one to eight waves per block."""
@@ -158,7 +159,7 @@ def test_seq_sigma_fused_vs_oracle(agg, H, Fo, chunk, monkeypatch):
 
 @pytest.mark.parametrize("chunk", [256, 64, 4])
 @pytest.mark.parametrize("act", ["leaky", "relu", "gelu", "identity", "gelu_tanh"])
-@pytest.mark.parametrize("H,O", [(256, 40), (64, 64), (300, 24), (128, 256), (100, 200), (512, 512)])
+@pytest.mark.parametrize("H,O", wc.MAX_PARITY_SHAPES)
 def test_max_fused_vs_oracle_first_wins(act, H, O, chunk, monkeypatch):
     """Fused forward for H, O <= 512 (roman-empire: H = O = 512, heterophilous-datasets/README.md:8)
     and, for H, O <= 256, the fused backward (forced: the memory budget picks the edge-materialised
@@ -362,8 +363,7 @@ def _no_edge_buffers(monkeypatch):
 
 @pytest.mark.parametrize("chunk", [256, 64, 4])
 @pytest.mark.parametrize("act", ["leaky", "relu", "gelu", "identity", "gelu_tanh"])
-@pytest.mark.parametrize("H,O", [(256, 256), (256, 40), (64, 64), (300, 24), (128, 256), (100, 200), (512, 256),
-                                 (4, 1)])
+@pytest.mark.parametrize("H,O", wc.MAX_ROUTED_SHAPES)
 def test_max_routed_backward_vs_oracle_first_wins(act, H, O, chunk, monkeypatch):
     """The routed max backward (sir_edge_max_bwd_sparse, opt-in for H % 4 == 0, H <= 512, O <= 256):
     dY reaches each (v, o)'s first arg-max edge only, dA from the routed W_R rows, no [E, *] buffer —

@@ -27,7 +27,7 @@ DEV = "cuda"
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 ACT = {"relu": (_native.ACT_RELU, 0.0), "leaky": (_native.ACT_LEAKY, xc.SLOPE)}
 ACT_MODULE = {"relu": nn.ReLU, "leaky": lambda: nn.LeakyReLU(xc.SLOPE)}
-GRAPH_AGG = [(g, a) for g in ("A", "B") for a in xc.AGGS_OF[g]]
+GRAPH_AGG = xc.GRAPH_AGG
 NAN = float("nan")
 _PLANS = {}
 
@@ -46,7 +46,7 @@ def _plan(graph, chunk):
 
 
 def _graphs(agg):
-    return [g for g in ("A", "B") if agg in xc.AGGS_OF[g]]
+    return xc.graphs_of(agg)
 
 
 def _want(t64, dtype=torch.float32):
@@ -135,6 +135,34 @@ def test_edge_kernels_exact(dt, H, agg, act):
                 dQK = _edge_backward(plan, H, agg, act, G, Q, K, m, dual, dtype)
                 _same(dQK[:, :H], wdQ, f"{what} {name} dQ")
                 _same(dQK[:, H:], wdK, f"{what} {name} dK")
+
+
+@pytest.mark.parametrize("act", xc.ACT_NAMES)
+@pytest.mark.parametrize("agg", ["sum", "mean", "sym"])
+@pytest.mark.parametrize("H", xc.EDGE_H_UNALIGNED)
+def test_edge_kernels_exact_unaligned_leading_dimension(H, agg, act):
+    """Q and K as column blocks of one [V, 2 H + 1] buffer (NaN in the spare column): rows of H % 4 == 0 values
+    that are not 16-B aligned take the scalar kernels with every lane's every slot full (H = 64, 128, 256: one,
+    two, four values per lane).  The forward and both recompute backward passes equal the fp64 oracle."""
+    code, slope = ACT[act]
+    for graph in _graphs(agg):
+        Q, K, G, _ = (t.to(DEV) for t in xc.edge_inputs(graph, H))
+        buf = torch.full((Q.shape[0], 2 * H + 1), NAN, device=DEV)
+        buf[:, :H], buf[:, H + 1:] = Q, K
+        Qv, Kv = buf[:, :H], buf[:, H + 1:]
+        assert Qv.stride(0) % 4 != 0 and Kv.data_ptr() % 16 != 0
+        wS, wdQ, wdK = (_want(t) for t in xc.edge_expected(graph, H, agg, act))
+        for chunk in (4, 64, 256):
+            plan = _plan(graph, chunk)
+            what = f"{graph} unaligned H={H} {agg} {act} chunk={chunk}"
+            in_norm, out_norm = plan.norms(agg)
+            S = torch.full((Q.shape[0], H), NAN, device=DEV)
+            part = torch.full((max(plan.dst.n_slots, plan.src.n_slots, 1) * H,), NAN, device=DEV)
+            _native.edge_agg_fwd(plan.dst, Qv, Kv, in_norm, out_norm, agg, code, slope, S, part, None)
+            _same(S, wS, what + " S")
+            dQK = _edge_backward(plan, H, agg, act, G, Qv, Kv, None, True, torch.float32)
+            _same(dQK[:, :H], wdQ, what + " recompute dQ")
+            _same(dQK[:, H:], wdK, what + " recompute dK")
 
 
 @pytest.mark.parametrize("act", xc.ACT_NAMES)
@@ -255,7 +283,7 @@ def _edge_ids(plan, arg):
 
 
 @pytest.mark.parametrize("act", xc.ACT_NAMES)
-@pytest.mark.parametrize("graph", ["A", "B"])
+@pytest.mark.parametrize("graph", list(xc.GRAPHS))
 @pytest.mark.parametrize("H,O", xc.MAX_SHAPES)
 def test_max_forward_exact_first_edge_wins(H, O, graph, act, monkeypatch):
     """The max forward (per-item kernel at chunk 4 / 64 / 256, the stream kernel at H = 256; fp32 and the two
@@ -289,7 +317,7 @@ MAX_ROUTES = {
 
 
 @pytest.mark.parametrize("act", xc.ACT_NAMES)
-@pytest.mark.parametrize("graph", ["A", "B"])
+@pytest.mark.parametrize("graph", list(xc.GRAPHS))
 @pytest.mark.parametrize("H,O", xc.MAX_SHAPES)
 def test_max_backward_routes_exact(H, O, graph, act, monkeypatch):
     """Every max backward route within its limits — routed (sir_edge_max_bwd_sparse + its dW pass), fused
@@ -322,7 +350,7 @@ def test_max_backward_routes_exact(H, O, graph, act, monkeypatch):
 
 
 @pytest.mark.parametrize("graph,agg", GRAPH_AGG)
-@pytest.mark.parametrize("F", [3, 64, 300])
+@pytest.mark.parametrize("F", xc.HELPER_F)
 def test_edge_materialised_helpers_exact(F, graph, agg):
     """sirgcn.generic on integers: sir_edge_gather_add, sir_segment_sum (plain, with norms / mean, and the
     ``perm`` form of the source side), sir_edge_broadcast, sir_segment_max / _bwd."""

@@ -12,7 +12,7 @@ import oracle
 
 Z0_FLOOR = 0.05
 TIE_FLOOR = 0.25
-GRAPH_AGG = [(g, a) for g in ("A", "B") for a in xc.AGGS_OF[g]]
+GRAPH_AGG = xc.GRAPH_AGG
 
 
 def _edge_act(Q, K, graph, act):
@@ -48,6 +48,33 @@ def test_graphs_are_what_the_cases_need():
     assert pairs.unique().numel() < pairs.numel()               # duplicate edges
 
 
+def test_graph_c_is_a_degree_ladder():
+    """Every row length 0..65 once on each side (tests/test_width_classes_cpu.py ties them to the kernels' chunk
+    loops), self-loops, duplicate edges, isolated nodes, edge ids not in CSR order."""
+    L = xc.LADDER_C
+    src, dst, V = xc.GRAPHS["C"]
+    assert (L, V, src.numel()) == (66, 134, 4290)
+    ind, outd = torch.bincount(dst, minlength=V), torch.bincount(src, minlength=V)
+    assert ind[:L].tolist() == list(range(L)) and outd[L:2 * L].tolist() == list(range(L))
+    assert ind[2 * L:].sum() == 0 and outd[2 * L:].sum() == 0   # isolated nodes
+    assert bool((src[dst < L] < L).all()) and bool((dst[src >= L] >= L).all())
+    assert int((src == dst).sum()) == 65                        # self-loops
+    pairs = src * V + dst
+    assert pairs.numel() - pairs.unique().numel() == 946        # duplicate edges
+    assert not torch.equal(dst, dst.sort().values)
+    assert xc.AGGS_OF["C"] == ("sum",)                          # mean and sym are not dyadic on it
+
+
+def test_graph_c_sums_survive_one_rounding_to_16_bits():
+    """max |S| on graph C is 520 at the full width: finite, and an fp32 number, after the 16-bit kernels' one
+    rounding of the output."""
+    for act in xc.ACT_NAMES:
+        S = xc.edge_expected("C", xc.WIDTH, "sum", act)[0]
+        assert float(S.abs().max()) == 520.0
+        for dt in (torch.bfloat16, torch.float16):
+            assert bool(torch.isfinite(S.float().to(dt)).all())
+
+
 @pytest.mark.parametrize("act", xc.ACT_NAMES)
 @pytest.mark.parametrize("graph,agg", GRAPH_AGG)
 def test_edge_kernel_inputs(graph, agg, act):
@@ -63,7 +90,7 @@ def test_edge_kernel_inputs(graph, agg, act):
         if agg == "mean":           # g = G / deg is rounded to the storage type (include/sirconv.h): exact here
             deg = torch.bincount(xc.GRAPHS[graph][1], minlength=Q.shape[0]).clamp(min=1).float()[:, None]
             assert torch.equal((G / deg).to(dt).float(), G / deg)
-    for h in xc.EDGE_H + xc.EDGE_H_SCALAR:
+    for h in xc.EDGE_H + xc.EDGE_H_SCALAR + xc.EDGE_H_UNALIGNED:
         share = float((xc.edge_z(graph, h) == 0).float().mean())
         assert share >= Z0_FLOOR, f"{graph} H={h}: z == 0 on {share:.3f} of the pairs"
 
@@ -127,7 +154,7 @@ def test_identity_edge_kernel_inputs(graph, agg):
 
 
 @pytest.mark.parametrize("act", xc.ACT_NAMES)
-@pytest.mark.parametrize("graph", ["A", "B"])
+@pytest.mark.parametrize("graph", list(xc.GRAPHS))
 @pytest.mark.parametrize("H,O", xc.MAX_SHAPES)
 def test_max_inputs(H, O, graph, act):
     r32, r64 = xc.max_expected(graph, H, O, act, torch.float32), xc.max_expected(graph, H, O, act)

@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 import oracle
+import width_cases as wc
 from conftest import assert_close, assert_parity, golden_manifest, load_case, rel_err
 
 import sirgcn
@@ -124,7 +125,7 @@ def test_state_dict_keys_match_reference_layout():
     assert sum(p.numel() for p in m2.parameters()) == 3 * 256 * 256 + 2 * 256
 
 
-@pytest.mark.parametrize("H", [1, 3, 7, 16, 60, 64, 100, 128, 256, 260, 300, 512, 1000, 1024])
+@pytest.mark.parametrize("H", wc.HIDDEN_SIZES)
 @pytest.mark.parametrize("agg", ["sum", "mean", "sym"])
 def test_hidden_sizes_vs_oracle(H, agg):
     gen = torch.Generator().manual_seed(H * 7 + len(agg))
@@ -723,7 +724,7 @@ def _one_launch_vs_two_passes(agg, dtype, chunk, H):
     assert torch.isfinite(outs[0]).all()
 
 
-SIGN_MASK_WIDTHS = [4, 12, 32, 60, 64, 76, 80, 96, 128, 136, 256, 512, 776, 1024]
+SIGN_MASK_WIDTHS = wc.SIGN_MASK_WIDTHS
 
 
 @pytest.mark.parametrize("H", SIGN_MASK_WIDTHS)

@@ -13,6 +13,7 @@ import torch
 from conftest import assert_parity, rel_err
 
 import cs_cases as cs
+import width_cases as wc
 import sirgcn
 from sirgcn import Clamp, FixRows, Graph, _native, get_plan
 
@@ -99,7 +100,7 @@ def _same(a, b):
 
 
 # ------------------------------------------------------------------ 1. exact
-@pytest.mark.parametrize("F", [1, 3, 4, 40, 47, 64, 65, 256, 260, 300])
+@pytest.mark.parametrize("F", wc.LP_F)
 def test_unsplit_rows_equal_the_reference_bit_for_bit(F):
     for V in (1, 5, 67, 300):
         y0, yfix, idx = cs.inputs(V, F)
@@ -142,7 +143,7 @@ def test_label_spreading_fixtures(name):
 
 
 # ------------------------------------------------------------------ 2. split rows
-@pytest.mark.parametrize("F", [3, 40, 260])
+@pytest.mark.parametrize("F", wc.LP_F_SPLIT)
 @pytest.mark.parametrize("V", [1, 5, 67, 300])
 def test_split_rows_step_by_step(V, F):
     src, dst, deg = cs.case_graph(V, True)

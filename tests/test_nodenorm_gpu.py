@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from conftest import assert_parity
+import width_cases as wc
 
 import sirgcn
 from sirgcn import GetNorm, Graph, GraphBatchNorm, GraphLayerNorm, GraphNorm, SIRConv, _native
@@ -19,7 +20,7 @@ DEV = "cuda"
 R = _native.BN_SLAB_ROWS            # the BatchNorm kernels' slab (rows per partial)
 
 BN_SHAPES = [(M, N) for M in (2, R - 1, R, R + 1, 3 * R + 7) for N in (1, 3, 75, 95, 128, 256, 300)]
-LN_SHAPES = [(M, N) for M in (1, 67, 1000) for N in (1, 3, 4, 60, 75, 80, 256, 300, 512, 1024)]
+LN_SHAPES = wc.LN_SHAPES
 ACTS = {"relu": nn.ReLU, "leaky": lambda: nn.LeakyReLU(0.2), "identity": nn.Identity}
 
 
@@ -115,6 +116,13 @@ def _sliced(x, pad=3):
 @pytest.mark.parametrize("N", [128, 75])
 def test_column_slice_input(N):
     _bn_case(R + 1, N, wrap=_sliced)
+    _ln_case(67, N, wrap=_sliced)
+
+
+@pytest.mark.parametrize("N", wc.LN_UNALIGNED_N)
+def test_layer_norm_unaligned_rows(N):
+    """N % 4 == 0 rows behind an unaligned column slice: the scalar kernels with every lane's 1, 2, 4, 8, 16
+    values in use (N = 64 .. 1024)."""
     _ln_case(67, N, wrap=_sliced)
 
 

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from conftest import assert_close
+import width_cases as wc
 
 import sirgcn
 from sirgcn import Graph, GraphBatchNorm, GraphLayerNorm, GraphNorm, GetNorm, SIRConv, _native
@@ -25,9 +26,9 @@ DEV = "cuda"
 SEED = 0x1234_5678_9ABC
 
 # the smallest shapes at which each kernel's partition can go wrong (slab = 128 rows; float4 / scalar columns;
-# LayerNorm's 1, 2, 4, 16 vectors per lane; an empty, a one-node and a multi-chunk graph)
+# LayerNorm's every count of vectors per lane, tests/width_cases.py; an empty, a one-node and a multi-chunk graph)
 BN_SHAPES = [(2, 4), (129, 75), (257, 256), (130, 300)]
-LN_SHAPES = [(3, 1), (130, 75), (67, 256), (5, 1024)]
+LN_SHAPES = wc.STACKDROP_LN_SHAPES
 GN_SIZES = [0, 1, 7, 130, 33]
 GN_WIDTHS = [75, 256]
 ACTS = {"relu": nn.ReLU, "leaky": lambda: nn.LeakyReLU(0.2), "identity": nn.Identity}

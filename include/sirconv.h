@@ -628,6 +628,32 @@ int sir_graph_norm_act_drop_bwd(const int64_t* off, int64_t B, int64_t F, const 
                                 const sir_dropout_t* drop, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The elementwise tail of the pre-norm residual block (heterophilous-datasets/model.py:36-50: Linear ->
+ * dropout -> GELU; conv -> dropout -> GELU; Linear -> dropout -> + resid), one pass per direction: the dropout
+ * stands BEFORE the activation.  Added under ABI 17 (new symbols only).
+ *   forward : out = act(d) + R,  d = keep(row, col) ? Y * scale : +0     (R may be NULL: no add)
+ *   backward: dY  = keep(row, col) ? act'(d) D * scale : 0               (D = dout; dR is D itself, the caller's)
+ * keep, scale and the seed are sir_dropout_t's: element (row, col) of the [M, N] block draws the bits
+ * sir_dropout_apply writes for it at col0 = 0; no mask is stored, the backward recomputes it and d from Y.
+ * drop == NULL or p <= 0: out = act(Y) + R; p >= 1: out = act(+0) + R and dY = 0; a NaN p: SIR_EINVAL; seed_ptr
+ * as in sir_dropout_t.  Give each site a seed word no conv of the step uses.
+ * act: all five SIR_ACT_* (the GELUs by the formulas of the edge kernels).  Y and dY are `dtype` (SIR_DTYPE_F32 /
+ * BF16 / F16); R, out and D are `o_dtype`, which is SIR_DTYPE_F32 or `dtype` (anything else: SIR_EINVAL).  A value is
+ * rounded to its storage type where torch's separate kernels would store it (after the dropout, after the
+ * activation, after the add; the gradient after the cast of D to `dtype`, after act', after the scale), with fp32
+ * arithmetic in between: Identity / ReLU / LeakyReLU are bit-identical to the composed torch ops and their autograd.
+ * Non-finite values: a dropped element is a select, not a product — d = +0 whatever Y held (NaN, Inf) and
+ * dY = 0 whatever D held; a kept NaN or Inf propagates (ReLU(NaN) = NaN), and a NaN of R comes through where R
+ * holds it.
+ * N % 4 == 0, N <= 2^24; rows 16-B (fp32) or 8-B (16-bit) aligned, leading dimensions >= N and multiples of 4
+ * elements; M == 0 returns SIR_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int sir_drop_act_fwd(const void* Y, int64_t ldy, int dtype, const void* R, int64_t ldr, void* out, int64_t ldo,
+                     int o_dtype, int64_t M, int64_t N, int act, float slope, const sir_dropout_t* drop, void* stream);
+int sir_drop_act_bwd(const void* D, int64_t ldd, int o_dtype, const void* Y, int64_t ldy, int dtype, void* dY,
+                     int64_t lddy, int64_t M, int64_t N, int act, float slope, const sir_dropout_t* drop, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling: ogbg-molhiv/model.py:69,85, zinc/model.py:41,
  * super-pixel/model.py:28, hetero-edge-count/model.py:23,33; dgl.broadcast_nodes is the backward of SUM) on
  * a batched graph: graph b owns node rows [off[b], off[b+1]) of X [V, F] (off = int64 [B+1], off[B] = V, as

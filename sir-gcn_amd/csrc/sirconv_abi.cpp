@@ -1455,4 +1455,43 @@ int sir_dropout_apply(void* X, int64_t ldx, int64_t M, int64_t N, int dtype, int
                   nullptr);
 }
 
+// the checks sir_drop_act_fwd / _bwd share: the shape, the types and the activation
+static int check_drop_act(const char* fn, int64_t M, int64_t N, int dtype, int o_dtype, int act,
+                          const sir_dropout_t* drop) {
+    if (M < 0 || N <= 0 || N % 4 != 0 || N > (1 << 24)) return fail(SIR_EINVAL, fn, "bad shape (N % 4 == 0, N <= 2^24)");
+    if (dtype != SIR_DTYPE_F32 && dtype != SIR_DTYPE_BF16 && dtype != SIR_DTYPE_F16) return fail(SIR_EINVAL, fn, "bad dtype");
+    if (o_dtype != SIR_DTYPE_F32 && o_dtype != dtype)
+        return fail(SIR_EINVAL, fn, "R / out must be fp32 or the 16-bit type of Y");
+    if (act < SIR_ACT_IDENTITY || act > SIR_ACT_GELU_TANH) return fail(SIR_EINVAL, fn, "unknown activation");
+    return check_layer_drop(fn, drop);
+}
+
+// rows of `dtype` read in 4-element vectors: 16-B (fp32) or 8-B (16-bit) aligned, ld >= N and ld % 4 == 0
+static bool rows4_ok(const void* p, int64_t ld, int64_t N, int dtype) {
+    const uintptr_t mask = dtype == SIR_DTYPE_F32 ? 15u : 7u;
+    return ld >= N && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & mask) == 0;
+}
+
+int sir_drop_act_fwd(const void* Y, int64_t ldy, int dtype, const void* R, int64_t ldr, void* out, int64_t ldo,
+                     int o_dtype, int64_t M, int64_t N, int act, float slope, const sir_dropout_t* drop, void* stream) {
+    const char* fn = "sir_drop_act_fwd";
+    if (int rc = check_drop_act(fn, M, N, dtype, o_dtype, act, drop)) return rc;
+    if (M > 0 && (Y == nullptr || out == nullptr)) return fail(SIR_EINVAL, fn, "NULL buffer");
+    if (!rows4_ok(Y, ldy, N, dtype) || !rows4_ok(out, ldo, N, o_dtype) || (R != nullptr && !rows4_ok(R, ldr, N, o_dtype)))
+        return fail(SIR_EINVAL, fn, "rows: 16-B (fp32) / 8-B (16-bit) aligned, ld >= N, ld % 4 == 0");
+    return finish(fn, sir::run_drop_act_fwd(Y, ldy, dtype, R, ldr, out, ldo, o_dtype, M, (int)N, act, slope,
+                                            to_drop(drop, 0), static_cast<hipStream_t>(stream)), nullptr);
+}
+
+int sir_drop_act_bwd(const void* D, int64_t ldd, int o_dtype, const void* Y, int64_t ldy, int dtype, void* dY,
+                     int64_t lddy, int64_t M, int64_t N, int act, float slope, const sir_dropout_t* drop, void* stream) {
+    const char* fn = "sir_drop_act_bwd";
+    if (int rc = check_drop_act(fn, M, N, dtype, o_dtype, act, drop)) return rc;
+    if (M > 0 && (D == nullptr || Y == nullptr || dY == nullptr)) return fail(SIR_EINVAL, fn, "NULL buffer");
+    if (!rows4_ok(D, ldd, N, o_dtype) || !rows4_ok(Y, ldy, N, dtype) || !rows4_ok(dY, lddy, N, dtype))
+        return fail(SIR_EINVAL, fn, "rows: 16-B (fp32) / 8-B (16-bit) aligned, ld >= N, ld % 4 == 0");
+    return finish(fn, sir::run_drop_act_bwd(D, ldd, o_dtype, Y, ldy, dtype, dY, lddy, M, (int)N, act, slope,
+                                            to_drop(drop, 0), static_cast<hipStream_t>(stream)), nullptr);
+}
+
 }  // extern "C"

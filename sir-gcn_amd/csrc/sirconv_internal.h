@@ -292,6 +292,12 @@ hipError_t run_gemm_nt16(const void* A, int64_t lda, int a_dtype, int64_t M, int
 // feature dropout applied in place to an [M, N] block of QK (the forward of paths whose QK GEMM
 // is not native): X[m][n] = keep(m, col0 + n) ? X[m][n] * scale : 0, storage dtype SIR_DTYPE_*
 hipError_t run_dropout_apply(void* X, int64_t ldx, int64_t M, int N, int dtype, const Drop& drop, hipStream_t st);
+// the pre-norm block's tail (sirconv_dropact.hip): out = act(dropout(Y)) + R and its backward; dtype: Y / dY,
+// o_dtype: R, out and D (SIR_DTYPE_F32 or dtype)
+hipError_t run_drop_act_fwd(const void* Y, int64_t ldy, int dtype, const void* R, int64_t ldr, void* O, int64_t ldo,
+                            int o_dtype, int64_t M, int N, int act, float slope, const Drop& drop, hipStream_t st);
+hipError_t run_drop_act_bwd(const void* D, int64_t ldd, int o_dtype, const void* Y, int64_t ldy, int dtype, void* DY,
+                            int64_t lddy, int64_t M, int N, int act, float slope, const Drop& drop, hipStream_t st);
 
 // compute units of the current device (persistent-grid sizing), queried once per device: the
 // attribute query is not free and the launch paths run it on every call otherwise

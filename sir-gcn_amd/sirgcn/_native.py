@@ -95,6 +95,8 @@ SIGNATURES = {
     "sir_gemm_pack16": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _P]),
     "sir_gemm_nt16": (ctypes.c_int, [_P, _I64, _I, _I64, _I64, _P, _I64, _I, _P, _P, _I64, _I, _P, _I64, _P, _P]),
     "sir_dropout_apply": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I64, _P, _P]),
+    "sir_drop_act_fwd": (ctypes.c_int, [_P, _I64, _I, _P, _I64, _P, _I64, _I, _I64, _I64, _I, _F, _P, _P]),
+    "sir_drop_act_bwd": (ctypes.c_int, [_P, _I64, _I, _P, _I64, _I, _P, _I64, _I64, _I64, _I, _F, _P, _P]),
     "sir_edge_agg_fwd": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I64, _I, _P, _I64, _P, _I64,
                                         _P, _P, _I, _I, _F, _P, _I64, _P, _P, _P]),
     "sir_edge_agg_bwd_dst": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I64, _I, _P, _I64, _P, _I64, _P,
@@ -971,6 +973,32 @@ def dropout_apply(X, drop, col0=0):
         rc = lib.sir_dropout_apply(_ptr(X), X.stride(0), M, N, STORAGE[X.dtype], col0, _drop(drop), _stream(X.device))
     _check(rc, lib)
     return X
+
+
+def drop_act_fwd(Y, R, act, slope, out, drop=None):
+    """out = act(dropout(Y)) + R in one pass (``sir_drop_act_fwd``; R may be None).  ``drop`` = (seed, p) as for
+    :func:`dropout_apply` (None: no dropout), the bits of an [M, N] block at col0 = 0.  Y fp32 / bf16 / fp16;
+    R and out share fp32 or Y's 16-bit type."""
+    lib = _lib if _lib is not None else load()
+    M, N = Y.shape
+    if R is not None and R.dtype is not out.dtype:
+        raise RuntimeError("drop_act_fwd: R and out must share one dtype")
+    with _Timed("sir_drop_act_fwd", out.device):
+        rc = lib.sir_drop_act_fwd(_ptr(Y), Y.stride(0), STORAGE[Y.dtype], _ptr(R), R.stride(0) if R is not None else 0,
+                                  _ptr(out), out.stride(0), STORAGE[out.dtype], M, N, int(act), float(slope),
+                                  _drop(drop), _stream(out.device))
+    _check(rc, lib)
+
+
+def drop_act_bwd(D, Y, act, slope, dY, drop=None):
+    """Backward of :func:`drop_act_fwd` (``sir_drop_act_bwd``, the same ``drop``: the mask is recomputed): dY in
+    Y's type from D, the gradient of ``out`` in its type.  R's gradient is D itself."""
+    lib = _lib if _lib is not None else load()
+    M, N = Y.shape
+    with _Timed("sir_drop_act_bwd", dY.device):
+        rc = lib.sir_drop_act_bwd(_ptr(D), D.stride(0), STORAGE[D.dtype], _ptr(Y), Y.stride(0), STORAGE[Y.dtype],
+                                  _ptr(dY), dY.stride(0), M, N, int(act), float(slope), _drop(drop), _stream(dY.device))
+    _check(rc, lib)
 
 
 def max_dw_rows(dcsr, arg, dY, A, O):

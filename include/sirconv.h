@@ -27,13 +27,16 @@
  *    into all three: sir_{batch,layer,graph}_norm_act_drop_fwd / _bwd;
  *  - the graph readout (dgl.nn.SumPooling / AvgPooling / MaxPooling, dgl.broadcast_nodes; ogbg-molhiv/model.py:69,85,
  *    zinc/model.py:41): sir_graph_pool_fwd / _bwd (sir_graph_pool_work_floats, sir_graph_pool_slab_rows);
+ *  - the L1 / L2 parameter penalty of the training loops (`regularizer`, benchmark-datasets/zinc/train.py:49-52):
+ *    sir_param_norms_fwd / _bwd, one multi-tensor pass per direction;
  *  - Correct & Smooth's label propagation (ogbn-arxiv/correct_and_smooth.py:41-58): sir_label_prop_step;
  *  - the graph input (DGL's CSC build for batched graphs): sir_csr_build / sir_csr_perm, and the per-layer
  *    DropEdge (models/utils.py:96-102) derived from a built plan: sir_plan_drop_edges.
  *
  * Conventions
  *  - All pointers are DEVICE pointers; all work is enqueued on `stream` (a hipStream_t,
- *    NULL = default stream); calls are asynchronous, stateless and reentrant.
+ *    NULL = default stream); calls are asynchronous, stateless and reentrant.  The one exception:
+ *    sir_param_norms_fwd / _bwd take HOST arrays of device addresses and counts (stated there).
  *  - The caller owns every buffer.  Outputs are fully overwritten (no pre-zeroing).
  *  - Row-major feature matrices with explicit leading dimensions (elements).
  *  - Graph structure is a "row CSR": rows are the nodes being reduced INTO, `col` holds the
@@ -63,6 +66,10 @@
  *    NaN, as arg; a row with edges always returns one of its edges (all -Inf: -Inf and the first edge),
  *    only a row without edges returns 0 / -1.  The rule does not depend on the plan's chunk, the
  *    route, or the readout's slab cut.
+ *    Parameter norms (sir_param_norms_fwd / _bwd): isolation covers the workspace, the bytes around a 4-B
+ *    aligned view and the gaps between gradient slots; every term of both sums is non-negative, so a NaN
+ *    parameter gives NaN in both, +-Inf (or both infinities) +Inf in both; the backward's expression is
+ *    evaluated as written, an absent g1 / g2 term is left out by selection.
  *    Deviations from torch: (1) a dropped element of the feature dropout, and of the layer dropout of
  *    sir_batch_norm_act_drop_* / sir_layer_norm_act_drop_* / sir_graph_norm_act_drop_* (forward: +0 before
  *    the add of R, which propagates; backward: g0 = 0), is 0 whatever it held
@@ -691,6 +698,52 @@ int sir_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int 
                        const void* X, int64_t ldx, void* P, int64_t ldp, int32_t* arg, float* work, void* stream);
 int sir_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int op, int dtype,
                        const void* dP, int64_t ldg, const int32_t* arg, void* dX, int64_t lddx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * L1 / L2 parameter penalty — the `regularizer(model, args)` of the reference's training loops
+ * (benchmark-datasets/zinc/train.py:49-52 and its six siblings):
+ *     (l1 * sum_p sum|p| + l2 * sum_p sum p^2) * int(model.training)   over model.parameters()
+ * as one multi-tensor pass per direction over fp32 tensors.  Added under ABI 17 (new symbols only).
+ *   forward : out2[0] = L1 = sum_t sum_i |p_t[i]|,  out2[1] = L2 = sum_t sum_i p_t[i]^2
+ *   backward: dP_t[i] = fl(g1 * sgn(p_t[i])) + fl(g2 * fl(2 * p_t[i])),  sgn(+-0) = 0, evaluated as written
+ *             (no FMA): bit for bit what autograd gives through the torch composition.
+ * HOST ARRAYS — the one exception to "all pointers are device pointers": `params`, `numel` and `grads` are
+ * HOST arrays of T entries, read during the call (they may be freed or changed after it returns); params[t]
+ * and grads[t] hold DEVICE addresses, numel[t] element counts.  work, out2, g1 and g2 are device pointers.
+ *   params[t]: numel[t] contiguous fp32, 4-B aligned (a view need not be 16-B aligned: only the aligned
+ *              body of a tensor is read with 16-B loads, its first and last 0..3 elements with 4-B loads).
+ *   grads[t] : the slot that receives dP_t, numel[t] fp32, 16-B aligned; NULL = no slot (a frozen
+ *              parameter): the tensor is skipped without being read.
+ *   g1, g2   : device fp32 scalars, the gradients of L1 and L2.  Either may be NULL: its term is left out
+ *              by selection, never multiplied by zero.  Both NULL is SIR_EINVAL.
+ * The device addresses and counts of up to sir_param_norms_max_tensors() = SIR_PARAM_NORMS_MAX_TENSORS
+ * tensors travel in one launch's kernel arguments (no device-side table), a longer list takes further
+ * launches.  A tensor is cut into chunks of sir_param_norms_chunk() = SIR_PARAM_NORMS_CHUNK elements counted
+ * from its own first element; the forward leaves one fp32 pair per chunk in `work` and a last one-block launch
+ * (sir_param_norms_combine_threads() threads) adds the pairs in chunk order by a fixed tree.  No atomics, no
+ * host synchronisation (graph-capturable while the addresses stay valid); the results are a function of the
+ * list (order, sizes, each address modulo 16) alone.  fp32 accumulation; the longest chain of roundings
+ * behind a result is 14 + ceil(C / 256) - 1 + 8 for C chunks (37 for 2^24 elements in one tensor; at most 64
+ * for 2^24 elements in up to 6912 tensors) — csrc/sirconv_paramnorm.hip states it term by term.
+ * work: sir_param_norms_work_floats(C) floats, C = sum_t ceil(numel[t] / chunk) (2 per chunk, at least 2;
+ * -1 for C < 0 or C >= 2^40); work_floats is the size the caller provides.  The backward needs none.
+ * T == 0 or every count 0: a no-op that issues no work (out2 is NOT written; NULL arrays accepted for T == 0).
+ * Non-finite values: `work`'s previous content, the bytes around a view and the gaps between gradient slots
+ * may hold anything; nothing but out2, work[0 .. 2 C) and the slots' numel[t] floats is written.  A NaN
+ * parameter makes both sums NaN, a +-Inf one makes both +Inf (the terms are non-negative: never Inf - Inf);
+ * the backward returns what IEEE gives for its expression (g2 = 0 and p = Inf: NaN, as in torch).
+ * ------------------------------------------------------------------------------------------- */
+#define SIR_PARAM_NORMS_CHUNK 4096
+#define SIR_PARAM_NORMS_MAX_TENSORS 96
+#define SIR_PARAM_NORMS_COMBINE_THREADS 256
+int64_t sir_param_norms_chunk(void);
+int64_t sir_param_norms_max_tensors(void);
+int64_t sir_param_norms_combine_threads(void);
+int64_t sir_param_norms_work_floats(int64_t n_chunks);
+int sir_param_norms_fwd(const float* const* params, const int64_t* numel, int64_t T, float* work,
+                        int64_t work_floats, float* out2, void* stream);
+int sir_param_norms_bwd(const float* const* params, const int64_t* numel, float* const* grads, int64_t T,
+                        const float* g1, const float* g2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Correct & Smooth label propagation (ogbn-arxiv/correct_and_smooth.py:41-58, `label_spreading`): one step

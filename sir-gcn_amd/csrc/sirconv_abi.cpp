@@ -1141,6 +1141,67 @@ int sir_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int64_t F, int 
                                               static_cast<hipStream_t>(stream)), "too many slab slots for one launch");
 }
 
+// ------------------------------------------------------------------------------ L1 / L2 parameter penalty
+// The checks read the HOST arrays params / numel / grads (tools/abi_sanitize.cpp runs them under ASan);
+// *chunks = the list's chunk count.
+static int check_param_list(const char* fn, const float* const* params, const int64_t* numel, float* const* grads,
+                            bool want_grads, int64_t T, int64_t* chunks) {
+    if (T < 0) return fail(SIR_EINVAL, fn, "T must be >= 0");
+    *chunks = 0;
+    if (T == 0) return SIR_OK;
+    if (params == nullptr || numel == nullptr || (want_grads && grads == nullptr))
+        return fail(SIR_EINVAL, fn, "NULL host array with T > 0");
+    for (int64_t t = 0; t < T; ++t) {
+        if (numel[t] < 0) return fail(SIR_EINVAL, fn, "negative element count");
+        if (numel[t] > ((int64_t)1 << 40)) return fail(SIR_EINVAL, fn, "element count above 2^40");
+        if (numel[t] == 0) continue;
+        if (params[t] == nullptr) return fail(SIR_EINVAL, fn, "NULL parameter with a non-zero count");
+        if ((reinterpret_cast<uintptr_t>(params[t]) & 3u) != 0)
+            return fail(SIR_EINVAL, fn, "parameter address must be 4-B aligned");
+        if (want_grads && (reinterpret_cast<uintptr_t>(grads[t]) & 15u) != 0)
+            return fail(SIR_EINVAL, fn, "gradient slot must be 16-B aligned");
+        *chunks += sir::param_norms_chunks(numel[t]);
+        if (*chunks >= ((int64_t)1 << 40)) return fail(SIR_EINVAL, fn, "too many chunks");
+    }
+    return SIR_OK;
+}
+
+int64_t sir_param_norms_chunk(void) { return SIR_PARAM_NORMS_CHUNK; }
+int64_t sir_param_norms_max_tensors(void) { return SIR_PARAM_NORMS_MAX_TENSORS; }
+int64_t sir_param_norms_combine_threads(void) { return SIR_PARAM_NORMS_COMBINE_THREADS; }
+
+int64_t sir_param_norms_work_floats(int64_t n_chunks) {
+    if (n_chunks < 0 || n_chunks >= ((int64_t)1 << 40)) return -1;
+    return 2 * (n_chunks > 1 ? n_chunks : 1);
+}
+
+int sir_param_norms_fwd(const float* const* params, const int64_t* numel, int64_t T, float* work,
+                        int64_t work_floats, float* out2, void* stream) {
+    const char* fn = "sir_param_norms_fwd";
+    int64_t chunks = 0;
+    int rc = check_param_list(fn, params, numel, nullptr, false, T, &chunks);
+    if (rc != SIR_OK) return rc;
+    if (chunks == 0) return SIR_OK;
+    if (out2 == nullptr) return fail(SIR_EINVAL, fn, "out2 must be non-NULL");
+    if (work == nullptr || work_floats < sir_param_norms_work_floats(chunks))
+        return fail(SIR_EINVAL, fn, "work smaller than sir_param_norms_work_floats");
+    if ((reinterpret_cast<uintptr_t>(work) & 7u) != 0) return fail(SIR_EINVAL, fn, "work must be 8-B aligned");
+    return finish(fn, sir::run_param_norms_fwd(params, numel, T, work, out2, static_cast<hipStream_t>(stream)),
+                  "a tensor has too many chunks for one launch");
+}
+
+int sir_param_norms_bwd(const float* const* params, const int64_t* numel, float* const* grads, int64_t T,
+                        const float* g1, const float* g2, void* stream) {
+    const char* fn = "sir_param_norms_bwd";
+    int64_t chunks = 0;
+    int rc = check_param_list(fn, params, numel, grads, true, T, &chunks);
+    if (rc != SIR_OK) return rc;
+    if (chunks == 0) return SIR_OK;
+    if (g1 == nullptr && g2 == nullptr) return fail(SIR_EINVAL, fn, "g1 and g2 are both NULL");
+    return finish(fn, sir::run_param_norms_bwd(params, numel, grads, T, g1, g2, static_cast<hipStream_t>(stream)),
+                  "a tensor has too many chunks for one launch");
+}
+
 // ------------------------------------------------------------------------------ C&S label propagation
 int sir_label_prop_step(const int32_t* rowptr, const int32_t* col, const int32_t* items, int64_t n_items,
                         const int32_t* splits, int64_t n_splits, int64_t V, int64_t F,

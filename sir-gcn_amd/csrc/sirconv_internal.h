@@ -127,6 +127,13 @@ hipError_t run_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int F, i
 hipError_t run_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int F, int op, int dtype, const void* dP,
                               int64_t ldg, const int* arg, void* dX, int64_t lddx, hipStream_t st);
 
+// L1 / L2 parameter penalty (sirconv_paramnorm.hip): params, numel, grads are HOST arrays of T entries
+int64_t param_norms_chunks(int64_t numel);
+hipError_t run_param_norms_fwd(const float* const* params, const int64_t* numel, int64_t T, float* work, float* out2,
+                               hipStream_t st);
+hipError_t run_param_norms_bwd(const float* const* params, const int64_t* numel, float* const* grads, int64_t T,
+                               const float* g1, const float* g2, hipStream_t st);
+
 // one label-spreading step of Correct & Smooth (sirconv_labelprop.hip); the fields are sir_label_prop_step's
 struct LabelPropArgs {
     const int* rowptr;

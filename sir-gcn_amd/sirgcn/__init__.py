@@ -11,8 +11,9 @@ from .readout import SumPooling, AvgPooling, MaxPooling, readout_nodes, broadcas
 from .propagate import label_spreading, correct_and_smooth, Clamp, FixRows  # noqa: F401
 from .dropedge import DropEdge, drop_edges, drop_edge_keep  # noqa: F401
 from .prenorm import drop_act, PreNormSIRModel  # noqa: F401
+from .regularize import param_norms, regularizer  # noqa: F401
 from . import _native  # noqa: F401
 
-__all__ = ["drop_act", "PreNormSIRModel", "DropEdge", "drop_edges", "drop_edge_keep", "label_spreading", "correct_and_smooth", "Clamp", "FixRows",
+__all__ = ["param_norms", "regularizer", "drop_act", "PreNormSIRModel", "DropEdge", "drop_edges", "drop_edge_keep", "label_spreading", "correct_and_smooth", "Clamp", "FixRows",
 "SIRConv", "SIREConv", "GraphNorm", "GraphBatchNorm", "GraphLayerNorm", "GetNorm", "Graph", "GraphPlan", "RowCSR", "EdgeAggregate", "batch", "get_plan",
            "build_row_csr", "SumPooling", "AvgPooling", "MaxPooling", "readout_nodes", "broadcast_nodes"]

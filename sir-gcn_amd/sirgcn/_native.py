@@ -66,6 +66,12 @@ SIGNATURES = {
     "sir_graph_pool_work_floats": (ctypes.c_int64, [_I64, _I64, _I64, _I]),
     "sir_graph_pool_fwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _I64, _P, _P, _P]),
     "sir_graph_pool_bwd": (ctypes.c_int, [_P, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _P, _I64, _P]),
+    "sir_param_norms_chunk": (ctypes.c_int64, []),
+    "sir_param_norms_max_tensors": (ctypes.c_int64, []),
+    "sir_param_norms_combine_threads": (ctypes.c_int64, []),
+    "sir_param_norms_work_floats": (ctypes.c_int64, [_I64]),
+    "sir_param_norms_fwd": (ctypes.c_int, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "sir_param_norms_bwd": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _P]),
     "sir_label_prop_step": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I, _F, _F,
                                            _I, _F, _F, _P, _P, _I64, _P, _I64, _P, _P]),
     "sir_edge_gather_add": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
@@ -746,6 +752,49 @@ def graph_pool_bwd(off, dP, op, dX, arg=None):
     else:
         with _Timed("sir_graph_pool_bwd", dev):
             rc = lib.sir_graph_pool_bwd(*args)
+    if rc != 0:
+        _check(rc, lib)
+
+
+# ------------------------------------------------------------------------------ L1 / L2 parameter penalty
+def param_norms_chunk():
+    """Elements per chunk of the multi-tensor passes (``sir_param_norms_chunk``)."""
+    return int(load().sir_param_norms_chunk())
+
+
+def param_norms_work_floats(n_chunks):
+    n = int(load().sir_param_norms_work_floats(int(n_chunks)))
+    if n < 0:
+        raise RuntimeError(f"sir_param_norms_work_floats({n_chunks}): chunk count out of range")
+    return n
+
+
+def param_norms_fwd(params_arr, numel_arr, T, work, out2):
+    """out2 = {sum |p|, sum p^2} over the list (``sir_param_norms_fwd``).  ``params_arr`` / ``numel_arr`` are
+    HOST ctypes arrays of T device addresses / element counts; ``work`` and ``out2`` are fp32 device tensors."""
+    lib = _lib if _lib is not None else load()
+    dev = out2.device
+    args = (params_arr, numel_arr, T, work.data_ptr(), work.numel(), out2.data_ptr(), _stream_of(dev))
+    if _timing is None:
+        rc = lib.sir_param_norms_fwd(*args)
+    else:
+        with _Timed("sir_param_norms_fwd", dev):
+            rc = lib.sir_param_norms_fwd(*args)
+    if rc != 0:
+        _check(rc, lib)
+
+
+def param_norms_bwd(params_arr, numel_arr, grads_arr, T, g1, g2, device):
+    """The slots of ``grads_arr`` (HOST ctypes array of T device addresses, 0 = no slot) receive
+    g1 * sgn(p) + g2 * (2 p); ``g1`` / ``g2`` are 0-dim fp32 device tensors or None (``sir_param_norms_bwd``)."""
+    lib = _lib if _lib is not None else load()
+    args = (params_arr, numel_arr, grads_arr, T, None if g1 is None else g1.data_ptr(),
+            None if g2 is None else g2.data_ptr(), _stream_of(device))
+    if _timing is None:
+        rc = lib.sir_param_norms_bwd(*args)
+    else:
+        with _Timed("sir_param_norms_bwd", device):
+            rc = lib.sir_param_norms_bwd(*args)
     if rc != 0:
         _check(rc, lib)
 

@@ -167,6 +167,58 @@ int main() {
     }
     expect("pool_work_floats: range", (int)sir_graph_pool_work_floats(8, 2, 65537, SIR_POOL_SUM), -1);
     expect("pool_work_floats: one slab", (int)sir_graph_pool_work_floats(SIR_POOL_SLAB_ROWS, 2, 8, SIR_POOL_MAX), 0);
+    // L1 / L2 parameter penalty: params / numel / grads are HOST arrays the validation reads (exactly T entries
+    // each, so a read past the end is a sanitizer report); the addresses in them are never dereferenced
+    {
+        float* const a16 = reinterpret_cast<float*>(0x10000);             // fake device addresses
+        std::vector<const float*> P = {a16, a16 + 16, a16 + 33};          // the last: 4-B aligned only
+        std::vector<int64_t> N = {4, 0, 7};
+        std::vector<float*> G = {a16 + 64, nullptr, a16 + 128};
+        float* w = a16 + 1024;
+        float* o = a16 + 2048;
+        const int64_t wf = sir_param_norms_work_floats(2);
+        auto fwd = [&](const std::vector<const float*>& p, const std::vector<int64_t>& n, int64_t T, float* work,
+                       int64_t work_floats, float* out2) {
+            return sir_param_norms_fwd(p.empty() ? nullptr : p.data(), n.empty() ? nullptr : n.data(), T, work,
+                                       work_floats, out2, nullptr);
+        };
+        auto bwd = [&](const std::vector<const float*>& p, const std::vector<int64_t>& n, const std::vector<float*>& g,
+                       int64_t T, const float* g1, const float* g2) {
+            return sir_param_norms_bwd(p.empty() ? nullptr : p.data(), n.empty() ? nullptr : n.data(),
+                                       g.empty() ? nullptr : g.data(), T, g1, g2, nullptr);
+        };
+        const std::vector<const float*> noP;
+        const std::vector<int64_t> noN;
+        const std::vector<float*> noG;
+        expect("pn_fwd: negative T", fwd(P, N, -1, w, wf, o), SIR_EINVAL, "sir_param_norms_fwd: T must be");
+        expect("pn_fwd: negative count", fwd(P, {4, -1, 7}, 3, w, wf, o), SIR_EINVAL, "negative element count");
+        expect("pn_fwd: NULL params", fwd(noP, N, 3, w, wf, o), SIR_EINVAL, "NULL host array");
+        expect("pn_fwd: NULL numel", fwd(P, noN, 3, w, wf, o), SIR_EINVAL, "NULL host array");
+        expect("pn_fwd: NULL parameter", fwd({a16, nullptr, a16}, {4, 1, 7}, 3, w, wf, o), SIR_EINVAL, "NULL parameter");
+        expect("pn_fwd: 2-B aligned", fwd({a16, a16, reinterpret_cast<const float*>(0x10002)}, N, 3, w, wf, o), SIR_EINVAL,
+               "4-B aligned");
+        expect("pn_fwd: small work", fwd(P, N, 3, w, wf - 1, o), SIR_EINVAL, "work smaller");
+        expect("pn_fwd: NULL work", fwd(P, N, 3, nullptr, wf, o), SIR_EINVAL, "work smaller");
+        expect("pn_fwd: NULL out2", fwd(P, N, 3, w, wf, nullptr), SIR_EINVAL, "out2");
+        expect("pn_fwd: T = 0 is a no-op", fwd(noP, noN, 0, nullptr, 0, nullptr), SIR_OK);
+        expect("pn_fwd: all counts 0 is a no-op", fwd({nullptr, a16, reinterpret_cast<const float*>(0x10002)}, {0, 0, 0}, 3,
+                                                     nullptr, 0, nullptr), SIR_OK);
+        expect("pn_bwd: negative T", bwd(P, N, G, -1, f, f), SIR_EINVAL, "sir_param_norms_bwd: T must be");
+        expect("pn_bwd: negative count", bwd(P, {-4, 0, 7}, G, 3, f, f), SIR_EINVAL, "negative element count");
+        expect("pn_bwd: NULL grads array", bwd(P, N, noG, 3, f, f), SIR_EINVAL, "NULL host array");
+        expect("pn_bwd: NULL parameter", bwd({nullptr, a16, a16}, N, G, 3, f, f), SIR_EINVAL, "NULL parameter");
+        expect("pn_bwd: 2-B aligned", bwd({reinterpret_cast<const float*>(0x10002), a16, a16}, N, G, 3, f, f), SIR_EINVAL,
+               "4-B aligned");
+        expect("pn_bwd: slot not 16-B aligned", bwd(P, N, {a16 + 64, nullptr, a16 + 129}, 3, f, f), SIR_EINVAL,
+               "16-B aligned");
+        expect("pn_bwd: no gradient at all", bwd(P, N, G, 3, nullptr, nullptr), SIR_EINVAL, "both NULL");
+        expect("pn_bwd: T = 0 is a no-op", bwd(noP, noN, noG, 0, nullptr, nullptr), SIR_OK);
+        expect("pn_bwd: all counts 0 is a no-op", bwd(P, {0, 0, 0}, {a16 + 1, nullptr, nullptr}, 3, f, nullptr), SIR_OK);
+        expect("pn_work_floats: negative", (int)sir_param_norms_work_floats(-1), -1);
+        expect("pn_work_floats: no chunks", (int)sir_param_norms_work_floats(0), 2);
+        expect("pn_chunk", (int)sir_param_norms_chunk(), SIR_PARAM_NORMS_CHUNK);
+        expect("pn_max_tensors", (int)sir_param_norms_max_tensors(), SIR_PARAM_NORMS_MAX_TENSORS);
+    }
     // C&S label propagation: f / f2 / f3 stand for Y / Y0 / out (out must differ from Y)
     {
         float* f2 = f + 16;

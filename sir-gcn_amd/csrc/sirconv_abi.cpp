@@ -16,6 +16,9 @@
 
 namespace {
 
+using sir::aligned16;
+using sir::aligned_to;
+
 thread_local std::string g_last_error;
 
 int fail(int code, const char* fn, const char* msg) {
@@ -544,7 +547,6 @@ int sir_segment_max_bwd(const int32_t* items, int64_t n_items, int64_t F, const 
 }
 
 // ------------------------------------------------------------------------------ fused per-edge dense layer
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static int check_mlp(const char* fn, const int32_t* rowptr, const int32_t* items, int64_t n_items,
                      const int32_t* splits, int64_t n_splits, int64_t H, int64_t F, const float* Q, int64_t ldq,
@@ -563,7 +565,7 @@ static int check_mlp(const char* fn, const int32_t* rowptr, const int32_t* items
         if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || (reinterpret_cast<uintptr_t>(Q) & 7u) ||
             (reinterpret_cast<uintptr_t>(K) & 7u))
             return fail(SIR_EUNSUPPORTED, fn, "Q/K rows must be 8-B aligned (ld % 4 == 0, ld >= H)");
-    } else if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !al16(Q) || !al16(K)) {
+    } else if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !aligned16(Q) || !aligned16(K)) {
         return fail(SIR_EUNSUPPORTED, fn, "Q/K rows must be 16-B aligned (ld % 4 == 0, ld >= H)");
     }
     if (n_splits > 0 && splits == nullptr) return fail(SIR_EINVAL, fn, "NULL splits");
@@ -580,7 +582,7 @@ int64_t sir_edge_mlp_pack_bytes(int64_t H, int64_t F) {
 int sir_edge_mlp_pack(const float* W, int64_t H, int64_t F, void* packed, void* stream) {
     const char* fn = "sir_edge_mlp_pack";
     if (H <= 0 || F <= 0 || H > 512 || F > 512) return fail(SIR_EINVAL, fn, "H <= 512, F <= 512");
-    if (W == nullptr || packed == nullptr || !al16(packed)) return fail(SIR_EINVAL, fn, "NULL / unaligned buffer");
+    if (W == nullptr || packed == nullptr || !aligned16(packed)) return fail(SIR_EINVAL, fn, "NULL / unaligned buffer");
     return finish(fn, sir::run_mlp_pack(W, (int)H, (int)F, packed, static_cast<hipStream_t>(stream)), nullptr);
 }
 
@@ -627,7 +629,7 @@ int sir_edge_mlp_fwd_stream(const int32_t* rowptr, const int32_t* col, const int
         return fail(SIR_EINVAL, fn, "NULL buffer / ldo");
     if (n_edges > 0 && (col == nullptr || erow == nullptr || Q == nullptr || K == nullptr))
         return fail(SIR_EINVAL, fn, "NULL col / erow / Q / K");
-    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !al16(Q) || !al16(K))
+    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !aligned16(Q) || !aligned16(K))
         return fail(SIR_EUNSUPPORTED, fn, "Q/K rows must be 16-B aligned (ld % 4 == 0, ld >= H)");
     if (agg == SIR_AGG_MAX && n_rows > 0 && (arg == nullptr || lda < F)) return fail(SIR_EINVAL, fn, "MAX needs arg");
     if (agg == SIR_AGG_SYM && n_edges > 0 && (norm_row == nullptr || norm_col == nullptr))
@@ -644,7 +646,7 @@ int sir_edge_mlp_pack_st(const float* W, int64_t H, int64_t F, int dtype, void* 
     const char* fn = "sir_edge_mlp_pack_st";
     if (H <= 0 || F <= 0 || H > 512 || F > 512) return fail(SIR_EINVAL, fn, "H <= 512, F <= 512");
     if (dtype != SIR_DTYPE_BF16 && dtype != SIR_DTYPE_F16) return fail(SIR_EINVAL, fn, "dtype must be BF16 or F16");
-    if (W == nullptr || packed == nullptr || !al16(packed)) return fail(SIR_EINVAL, fn, "NULL / unaligned buffer");
+    if (W == nullptr || packed == nullptr || !aligned16(packed)) return fail(SIR_EINVAL, fn, "NULL / unaligned buffer");
     return finish(fn, sir::run_mlp_pack_st(W, (int)H, (int)F, dtype, packed, static_cast<hipStream_t>(stream)), nullptr);
 }
 
@@ -760,7 +762,7 @@ int sir_edge_max_bwd_dst(const int32_t* rowptr, const int32_t* col, const int32_
     if (act1 < SIR_ACT_IDENTITY || act1 > SIR_ACT_GELU_TANH) return fail(SIR_EINVAL, fn, "unknown act1");
     if (H <= 0 || H % 4 != 0 || H > 256 || O <= 0 || O > 256) return fail(SIR_EUNSUPPORTED, fn, "H % 4 == 0, H <= 256, O <= 256");
     if (n_items < 0 || n_splits < 0 || n_items > INT32_MAX) return fail(SIR_EINVAL, fn, "bad item count");
-    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !al16(Q) || !al16(K))
+    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !aligned16(Q) || !aligned16(K))
         return fail(SIR_EUNSUPPORTED, fn, "Q/K rows must be 16-B aligned (ld % 4 == 0, ld >= H)");
     if (n_items > 0 && (rowptr == nullptr || items == nullptr || Q == nullptr || K == nullptr || dY == nullptr ||
                         ldy < O || arg == nullptr || lda < O || W == nullptr || dQ == nullptr || lddq < H ||
@@ -809,8 +811,8 @@ int sir_edge_max_bwd_sparse(const int32_t* rowptr_d, const int32_t* col_d, const
         n_items_d > INT32_MAX || n_items_s > INT32_MAX || E > INT32_MAX)
         return fail(SIR_EINVAL, fn, "bad size");
     if (V * O >= (int64_t)INT32_MAX) return fail(SIR_EUNSUPPORTED, fn, "V * O must be < 2^31");
-    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || lddq < H || lddk < H || lddq % 4 || lddk % 4 || !al16(Q) ||
-        !al16(K) || !al16(W) || !al16(dQ) || !al16(dK))
+    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || lddq < H || lddk < H || lddq % 4 || lddk % 4 || !aligned16(Q) ||
+        !aligned16(K) || !aligned16(W) || !aligned16(dQ) || !aligned16(dK))
         return fail(SIR_EUNSUPPORTED, fn, "Q / K / W / dQ / dK rows must be 16-B aligned (ld % 4 == 0, ld >= H)");
     if (V > 0 && (rowptr_d == nullptr || items_d == nullptr || Q == nullptr || dY == nullptr || ldy < O ||
                   arg == nullptr || lda < O || W == nullptr || dQ == nullptr || dbpart == nullptr ||
@@ -845,7 +847,7 @@ int sir_max_dw_rows(const int32_t* rowptr, int64_t V, const int32_t* arg, int64_
     if (O <= 0 || O > 256 || H <= 0 || H % 4 != 0 || H > INT32_MAX) return fail(SIR_EUNSUPPORTED, fn, "O <= 256, H % 4 == 0");
     if (V < 0 || V > INT32_MAX) return fail(SIR_EINVAL, fn, "bad V");
     if (ldw < O * H + ((O + 3) / 4) * 4 || ldw % 4) return fail(SIR_EINVAL, fn, "ldw >= O * H + O4, ldw % 4 == 0");
-    if (ldA < H || ldA % 4 || !al16(A) || !al16(wpart)) return fail(SIR_EUNSUPPORTED, fn, "A rows 16-B aligned");
+    if (ldA < H || ldA % 4 || !aligned16(A) || !aligned16(wpart)) return fail(SIR_EUNSUPPORTED, fn, "A rows 16-B aligned");
     if (V > 0 && (rowptr == nullptr || arg == nullptr || lda < O || dY == nullptr || ldy < O || wpart == nullptr))
         return fail(SIR_EINVAL, fn, "NULL buffer / leading dimension");
     return finish(fn, sir::run_max_dw_rows(rowptr, V, arg, lda, dY, ldy, A, ldA, (int)O, (int)H, wpart, ldw,
@@ -860,7 +862,7 @@ int sir_max_dw_qk(const int32_t* rowptr, const int32_t* col, int64_t V, const in
     if (O <= 0 || O > 256 || H <= 0 || H % 4 != 0 || H > INT32_MAX) return fail(SIR_EUNSUPPORTED, fn, "O <= 256, H % 4 == 0");
     if (V < 0 || V > INT32_MAX) return fail(SIR_EINVAL, fn, "bad V");
     if (ldw < O * H + ((O + 3) / 4) * 4 || ldw % 4) return fail(SIR_EINVAL, fn, "ldw >= O * H + O4, ldw % 4 == 0");
-    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !al16(Q) || !al16(K) || !al16(wpart))
+    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !aligned16(Q) || !aligned16(K) || !aligned16(wpart))
         return fail(SIR_EUNSUPPORTED, fn, "Q / K rows 16-B aligned");
     if (V > 0 && (rowptr == nullptr || col == nullptr || arg == nullptr || lda < O || dY == nullptr || ldy < O ||
                   wpart == nullptr))
@@ -878,7 +880,7 @@ int sir_edge_max_bwd_src(const int32_t* rowptr_s, const int32_t* col_s, const in
     if (act1 < SIR_ACT_IDENTITY || act1 > SIR_ACT_GELU_TANH) return fail(SIR_EINVAL, fn, "unknown act1");
     if (H <= 0 || H % 4 != 0 || H > 256 || O <= 0 || O > 256) return fail(SIR_EUNSUPPORTED, fn, "H % 4 == 0, H <= 256, O <= 256");
     if (n_items < 0 || n_splits < 0 || n_items > INT32_MAX) return fail(SIR_EINVAL, fn, "bad item count");
-    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !al16(Q) || !al16(K))
+    if (ldq < H || ldk < H || ldq % 4 || ldk % 4 || !aligned16(Q) || !aligned16(K))
         return fail(SIR_EUNSUPPORTED, fn, "Q/K rows must be 16-B aligned (ld % 4 == 0, ld >= H)");
     if (n_items > 0 && (rowptr_s == nullptr || items == nullptr || Q == nullptr || K == nullptr || dY == nullptr ||
                         ldy < O || arg == nullptr || lda < O || W == nullptr || dK == nullptr || lddk < H))
@@ -922,7 +924,7 @@ int sir_resid_act_fwd(const void* Y, int64_t ldy, int dtype, const float* R, int
     if (ldy < N || ldr < N || ldo < N || ldy % 4 || ldr % 4 || ldo % 4)
         return fail(SIR_EINVAL, fn, "leading dimensions must be >= N and multiples of 4");
     if (M > 0 && (Y == nullptr || R == nullptr || out == nullptr)) return fail(SIR_EINVAL, fn, "NULL buffer");
-    if (!al16(R) || !al16(out) || (dtype == SIR_DTYPE_F32 ? !al16(Y) : (reinterpret_cast<uintptr_t>(Y) & 7u) != 0))
+    if (!aligned16(R) || !aligned16(out) || !aligned_to(Y, dtype == SIR_DTYPE_F32 ? 16 : 8))
         return fail(SIR_EINVAL, fn, "rows must be 16-B aligned (8-B for 16-bit Y)");
     return finish(fn, sir::run_resid_act_fwd(Y, ldy, dtype, R, ldr, out, ldo, M, (int)N, act, slope, order,
                                              static_cast<hipStream_t>(stream)), nullptr);
@@ -937,7 +939,7 @@ int sir_resid_act_bwd(const float* D, int64_t ldd, const float* D2, int64_t ldd2
     if (act != SIR_ACT_IDENTITY && act != SIR_ACT_RELU && act != SIR_ACT_LEAKY_RELU)
         return fail(SIR_EINVAL, fn, "act must be identity, relu or leaky_relu");
     if (order != 0 && order != 1) return fail(SIR_EINVAL, fn, "order must be 0 (zinc) or 1 (arxiv)");
-    if (D2 != nullptr && (ldd2 < N || ldd2 % 4 || !al16(D2) || (order == 1 && dR == nullptr)))
+    if (D2 != nullptr && (ldd2 < N || ldd2 % 4 || !aligned16(D2) || (order == 1 && dR == nullptr)))
         return fail(SIR_EINVAL, fn, "D2: rows 16-B aligned, ldd2 >= N, ldd2 % 4 == 0 (order 1: with dR for the sum)");
     const bool want_dr = order == 0 || D2 != nullptr;        // order 1 writes dR only as the sum D + D2
     if (ldd < N || ldy < N || lddy < N || ldd % 4 || ldy % 4 || lddy % 4 || (order == 0 && (ldr < N || ldr % 4)) ||
@@ -945,9 +947,9 @@ int sir_resid_act_bwd(const float* D, int64_t ldd, const float* D2, int64_t ldd2
         return fail(SIR_EINVAL, fn, "leading dimensions must be >= N and multiples of 4");
     if (M > 0 && (D == nullptr || Y == nullptr || dY == nullptr || (order == 0 && R == nullptr)))
         return fail(SIR_EINVAL, fn, "NULL buffer");
-    const bool y16 = dtype != SIR_DTYPE_F32;
-    if (!al16(D) || (y16 ? (reinterpret_cast<uintptr_t>(Y) & 7u) || (reinterpret_cast<uintptr_t>(dY) & 7u)
-                         : !al16(Y) || !al16(dY)) || (order == 0 && !al16(R)) || (want_dr && !al16(dR)))
+    const uintptr_t yb = dtype == SIR_DTYPE_F32 ? 16 : 8;
+    if (!aligned16(D) || !aligned_to(Y, yb) || !aligned_to(dY, yb) || (order == 0 && !aligned16(R)) ||
+        (want_dr && !aligned16(dR)))
         return fail(SIR_EINVAL, fn, "rows must be 16-B aligned (8-B for 16-bit Y, dY)");
     return finish(fn, sir::run_resid_act_bwd(D, ldd, D2, ldd2, Y, ldy, dtype, R, ldr, dY, lddy, want_dr ? dR : nullptr, lddr, M,
                                              (int)N, act, slope, order, static_cast<hipStream_t>(stream)), nullptr);

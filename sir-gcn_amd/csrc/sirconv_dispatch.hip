@@ -140,8 +140,6 @@ hipError_t run_degree_norms(const int* rowptr_a, float* norm_a, const int* rowpt
     return hipGetLastError();
 }
 
-static bool aligned_to(const void* p, uintptr_t b) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (b - 1)) == 0; }
-
 // Vector width 4 needs every row start 16-B aligned (fp32) / 8-B aligned (16-bit).  (16-bit rows with
 // 8 values per lane on sub-wave rows were measured 2-3x slower on the power-law graph, forward slower on
 // molecule batches too: profiles/r04_ab_vw8_16bit.txt.)
@@ -171,7 +169,7 @@ hipError_t run_edge(int mode, int dtype, const EdgeArgs& a, int agg, int act,
     // 4-wide vectors need every feature row start aligned to 4 elements (16 B fp32, 8 B 16-bit)
     const uintptr_t vb = (dtype == ST_F32) ? 16 : 8;
     const bool v4 = aligned_to(a.R, vb) && aligned_to(a.C, vb) && aligned_to(a.G, vb) && aligned_to(a.out, vb) &&
-                    aligned_to(a.partial, 16) && aligned_to(a.Gm, vb) &&
+                    aligned16(a.partial) && aligned_to(a.Gm, vb) &&
                     (a.ldr % 4 == 0) && (a.ldc % 4 == 0) && (a.ldg % 4 == 0) && (a.ldo % 4 == 0) &&
                     (a.ldgm % 4 == 0);
     Shape s;
@@ -183,11 +181,9 @@ hipError_t run_edge(int mode, int dtype, const EdgeArgs& a, int agg, int act,
         *why = "bf16/fp16 storage needs H % 4 == 0 and 8-B aligned rows (leading dimensions multiples of 4)";
         return hipErrorInvalidValue;
     }
-    switch (dtype) {
-        case ST_BF16: return run_edge_t<ST_BF16>(mode, a, agg, act, s, splits, n_splits, out_final, ld_final, mean_div, st);
-        case ST_F16: return run_edge_t<ST_F16>(mode, a, agg, act, s, splits, n_splits, out_final, ld_final, mean_div, st);
-        default: return run_edge_t<ST_F32>(mode, a, agg, act, s, splits, n_splits, out_final, ld_final, mean_div, st);
-    }
+    return by_dtype(dtype, [&](auto dt) {
+        return run_edge_t<dt()>(mode, a, agg, act, s, splits, n_splits, out_final, ld_final, mean_div, st);
+    });
 }
 
 hipError_t run_edge_dual(int dtype, const EdgeArgs& a, const int32_t* splits, int64_t n_splits,
@@ -195,30 +191,23 @@ hipError_t run_edge_dual(int dtype, const EdgeArgs& a, const int32_t* splits, in
                          int agg, int act, hipStream_t st, const char** why) {
     const uintptr_t vb = (dtype == ST_F32) ? 16 : 8;
     const bool v4 = aligned_to(a.G, vb) && aligned_to(a.out, vb) && aligned_to(b.out, vb) &&
-                    aligned_to(a.partial, 16) && aligned_to(b.partial, 16) &&
+                    aligned16(a.partial) && aligned16(b.partial) &&
                     (a.ldg % 4 == 0) && (a.ldo % 4 == 0) && (b.ldo % 4 == 0);
     Shape s;
     if (!pick_shape(a.H, v4, &s) || s.vw != 4) {
         *why = "the sign-mask backward needs H % 4 == 0, H <= 1024 and aligned rows";
         return hipErrorInvalidValue;
     }
-    hipError_t err;
-    switch (dtype) {
-        case ST_BF16: err = launch_edge_dual<ST_BF16>(a, b, agg, act, s, st); break;
-        case ST_F16: err = launch_edge_dual<ST_F16>(a, b, agg, act, s, st); break;
-        default: err = launch_edge_dual<ST_F32>(a, b, agg, act, s, st); break;
-    }
+    hipError_t err = by_dtype(dtype, [&](auto dt) { return launch_edge_dual<dt()>(a, b, agg, act, s, st); });
     if (err != hipSuccess) {
         if (err == hipErrorInvalidValue) *why = "the one-launch backward covers SUM/SYM with ReLU/LeakyReLU only";
         return err;
     }
     auto combine = [&](const int32_t* sp, int64_t n, const EdgeArgs& x) -> hipError_t {
         if (n == 0) return hipSuccess;
-        switch (dtype) {
-            case ST_BF16: return launch_combine<ST_BF16, false>(sp, n, x.partial, x.H, x.out, x.ldo, 4, st, x.drop);
-            case ST_F16: return launch_combine<ST_F16, false>(sp, n, x.partial, x.H, x.out, x.ldo, 4, st, x.drop);
-            default: return launch_combine<ST_F32, false>(sp, n, x.partial, x.H, x.out, x.ldo, 4, st, x.drop);
-        }
+        return by_dtype(dtype, [&](auto dt) {
+            return launch_combine<dt(), false>(sp, n, x.partial, x.H, x.out, x.ldo, 4, st, x.drop);
+        });
     };
     if ((err = combine(splits, n_splits, a)) != hipSuccess) return err;
     return combine(splits_s, n_splits_s, b);

@@ -38,11 +38,6 @@ __device__ __forceinline__ mf16 mfma32(float a, float b, mf16 c) {
 // D-layout row (edge within the 32-edge tile) of accumulator register r in lane l
 __device__ __forceinline__ int drow(int r, int l) { return 8 * (r >> 2) + 4 * (l >> 5) + (r & 3); }
 
-template <int ACT>
-__device__ __forceinline__ float act_f(float z, float slope) {
-    return sig<ACT>(z, slope);
-}
-
 // ------------------------------------------------------------------------------ weight packing
 // Forward operand B[k][n] = W[n][k] (W: [F, H] row-major, an nn.Linear weight): float4 per lane,
 // packed[(t * (HP / 8) + q) * 64 + l] = {W[32t + l%32][8q + 2j + l/32], j = 0..3}, 0 outside.
@@ -244,10 +239,10 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
             for (int c = 0; c < C4; ++c) {
                 const int k = 256 * c + 4 * l;
                 const bool ok = i < nv && k < H;
-                a4[c].x = ok ? act_f<ACT1>(q4[c].x + kv[ii][c].x, slope) : 0.f;
-                a4[c].y = ok ? act_f<ACT1>(q4[c].y + kv[ii][c].y, slope) : 0.f;
-                a4[c].z = ok ? act_f<ACT1>(q4[c].z + kv[ii][c].z, slope) : 0.f;
-                a4[c].w = ok ? act_f<ACT1>(q4[c].w + kv[ii][c].w, slope) : 0.f;
+                a4[c].x = ok ? sig<ACT1>(q4[c].x + kv[ii][c].x, slope) : 0.f;
+                a4[c].y = ok ? sig<ACT1>(q4[c].y + kv[ii][c].y, slope) : 0.f;
+                a4[c].z = ok ? sig<ACT1>(q4[c].z + kv[ii][c].z, slope) : 0.f;
+                a4[c].w = ok ? sig<ACT1>(q4[c].w + kv[ii][c].w, slope) : 0.f;
                 m = fmaxf(m, fmaxf(fmaxf(fabsf(a4[c].x), fabsf(a4[c].y)), fmaxf(fabsf(a4[c].z), fabsf(a4[c].w))));
             }
             if constexpr (X16) {
@@ -320,7 +315,7 @@ k_mlp_fwd16(const int* __restrict__ rowptr, const int* __restrict__ col, const i
             for (int r = 0; r < 16; ++r) {
                 const int i = drow(r, l);
                 if (i < nv) {
-                    const float m = act_f<ACT2>(acc[j][r] * sInv[i] * iw[j] + bb[j], slope);
+                    const float m = sig<ACT2>(acc[j][r] * sInv[i] * iw[j] + bb[j], slope);
                     if constexpr (RED == 3) {
                         if (max_beats(m, best[j])) { best[j] = m; bidx[j] = t0 + i; }    // first wins
                     } else {
@@ -427,10 +422,10 @@ k_mlp_fwd16p(const int* __restrict__ rowptr, const int* __restrict__ col, const 
                 const int i = w + NW * ii;
                 const bool ok = i < nv && k4 < H;
                 float4 a4;
-                a4.x = ok ? act_f<ACT1>(q4.x + kv[ii].x, slope) : 0.f;
-                a4.y = ok ? act_f<ACT1>(q4.y + kv[ii].y, slope) : 0.f;
-                a4.z = ok ? act_f<ACT1>(q4.z + kv[ii].z, slope) : 0.f;
-                a4.w = ok ? act_f<ACT1>(q4.w + kv[ii].w, slope) : 0.f;
+                a4.x = ok ? sig<ACT1>(q4.x + kv[ii].x, slope) : 0.f;
+                a4.y = ok ? sig<ACT1>(q4.y + kv[ii].y, slope) : 0.f;
+                a4.z = ok ? sig<ACT1>(q4.z + kv[ii].z, slope) : 0.f;
+                a4.w = ok ? sig<ACT1>(q4.w + kv[ii].w, slope) : 0.f;
                 float m = fmaxf(fmaxf(fabsf(a4.x), fabsf(a4.y)), fmaxf(fabsf(a4.z), fabsf(a4.w)));
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
@@ -470,7 +465,7 @@ k_mlp_fwd16p(const int* __restrict__ rowptr, const int* __restrict__ col, const 
                 for (int r = 0; r < 16; ++r) {
                     const int i = drow(r, l);
                     if (i < nv) {
-                        const float m = act_f<ACT2>(acc[r] * sInv[i] * iwv + bbv, slope);
+                        const float m = sig<ACT2>(acc[r] * sInv[i] * iwv + bbv, slope);
                         if constexpr (RED == 3) {
                             if (max_beats(m, best)) { best = m; bidx = t0 + i; }    // first wins
                         } else {
@@ -637,10 +632,10 @@ k_mlp_fwd16q(const int* __restrict__ col, const int4* __restrict__ items, int64_
             const int i = w + NW * ii;
             const bool ok = i < nv && kin;
             float4 a4;
-            a4.x = ok ? act_f<ACT1>(q4.x + kv[ii].x, slope) : 0.f;
-            a4.y = ok ? act_f<ACT1>(q4.y + kv[ii].y, slope) : 0.f;
-            a4.z = ok ? act_f<ACT1>(q4.z + kv[ii].z, slope) : 0.f;
-            a4.w = ok ? act_f<ACT1>(q4.w + kv[ii].w, slope) : 0.f;
+            a4.x = ok ? sig<ACT1>(q4.x + kv[ii].x, slope) : 0.f;
+            a4.y = ok ? sig<ACT1>(q4.y + kv[ii].y, slope) : 0.f;
+            a4.z = ok ? sig<ACT1>(q4.z + kv[ii].z, slope) : 0.f;
+            a4.w = ok ? sig<ACT1>(q4.w + kv[ii].w, slope) : 0.f;
             const float m = wave_max64(fmaxf(fmaxf(fabsf(a4.x), fabsf(a4.y)), fmaxf(fabsf(a4.z), fabsf(a4.w))));
             const int se = mlp_scale_exp(m);
             const float sc = mlp_pow2(se);
@@ -706,7 +701,7 @@ k_mlp_fwd16q(const int* __restrict__ col, const int4* __restrict__ items, int64_
             for (int r = 0; r < 16; ++r) {
                 const int i = drow(r, l);
                 const float iv = r % 4 == 0 ? inv4[r / 4].x : r % 4 == 1 ? inv4[r / 4].y : r % 4 == 2 ? inv4[r / 4].z : inv4[r / 4].w;
-                const float m = act_f<ACT2>(acc[r] * iv * iwv + bbv, slope);
+                const float m = sig<ACT2>(acc[r] * iv * iwv + bbv, slope);
                 if constexpr (RED == 3) {
                     const bool take = i < nv && max_beats(m, best);         // first wins
                     best = take ? m : best;
@@ -861,10 +856,10 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
             const int i = w + NW * ii;
             const bool ok = i < nv;
             float4 a4;
-            a4.x = ok ? act_f<ACT1>(qv[ii].x + kv[ii].x, slope) : 0.f;
-            a4.y = ok ? act_f<ACT1>(qv[ii].y + kv[ii].y, slope) : 0.f;
-            a4.z = ok ? act_f<ACT1>(qv[ii].z + kv[ii].z, slope) : 0.f;
-            a4.w = ok ? act_f<ACT1>(qv[ii].w + kv[ii].w, slope) : 0.f;
+            a4.x = ok ? sig<ACT1>(qv[ii].x + kv[ii].x, slope) : 0.f;
+            a4.y = ok ? sig<ACT1>(qv[ii].y + kv[ii].y, slope) : 0.f;
+            a4.z = ok ? sig<ACT1>(qv[ii].z + kv[ii].z, slope) : 0.f;
+            a4.w = ok ? sig<ACT1>(qv[ii].w + kv[ii].w, slope) : 0.f;
             char* const d = img[bf] + sg * 2048 + mlp_fimg_sw(i, sh, sg) + sj8 * 2;
             if constexpr (X16) {
                 *reinterpret_cast<uint2*>(d) = pack4_st<ST>(a4);
@@ -923,10 +918,10 @@ k_mlp_fwd16r(const int* __restrict__ col, const int* __restrict__ erow, const in
             for (int g = 0; g < 4; ++g) {
                 const float4 iv = *reinterpret_cast<const float4*>(sInv[bf] + 8 * g + hb);
                 float4 o;
-                o.x = act_f<ACT2>(acc[4 * g + 0] * iv.x * iwv + bbv, slope);
-                o.y = act_f<ACT2>(acc[4 * g + 1] * iv.y * iwv + bbv, slope);
-                o.z = act_f<ACT2>(acc[4 * g + 2] * iv.z * iwv + bbv, slope);
-                o.w = act_f<ACT2>(acc[4 * g + 3] * iv.w * iwv + bbv, slope);
+                o.x = sig<ACT2>(acc[4 * g + 0] * iv.x * iwv + bbv, slope);
+                o.y = sig<ACT2>(acc[4 * g + 1] * iv.y * iwv + bbv, slope);
+                o.z = sig<ACT2>(acc[4 * g + 2] * iv.z * iwv + bbv, slope);
+                o.w = sig<ACT2>(acc[4 * g + 3] * iv.w * iwv + bbv, slope);
                 if constexpr (RED != 3) {
                     const float4 cv = *reinterpret_cast<const float4*>(sC[bf] + 8 * g + hb);
                     o.x = cv.x * o.x; o.y = cv.y * o.y; o.z = cv.z * o.z; o.w = cv.w * o.w;
@@ -1237,8 +1232,8 @@ k_mlp_bwd(const int* __restrict__ rowptr, const int* __restrict__ col, const int
                         // z = Q[v] + K[u] in the reference's operand order either way
                         z = DST ? make_float4(rv.x + ov.x, rv.y + ov.y, rv.z + ov.z, rv.w + ov.w)
                                 : make_float4(ov.x + rv.x, ov.y + rv.y, ov.z + rv.z, ov.w + rv.w);
-                        a = make_float4(act_f<ACT1>(z.x, slope), act_f<ACT1>(z.y, slope), act_f<ACT1>(z.z, slope),
-                                        act_f<ACT1>(z.w, slope));
+                        a = make_float4(sig<ACT1>(z.x, slope), sig<ACT1>(z.y, slope), sig<ACT1>(z.z, slope),
+                                        sig<ACT1>(z.w, slope));
                     }
                     float* dz = sZ + i * P + k4;
                     float* da = sA + i * P + k4;
@@ -1510,17 +1505,10 @@ hipError_t mlp_bwd_red(int red, dim3 grid, hipStream_t st, const EdgeMlpArgs& a)
 // act1 in {identity, relu, leaky, gelu, gelu_tanh} x act2 in {identity, relu}
 template <typename Fn>
 hipError_t by_acts(int act1, int act2, Fn&& fn) {
-#define SIR_ACT2(A1)                                                               \
-    return act2 == ACT_RELU ? fn(std::integral_constant<int, A1>{}, std::integral_constant<int, ACT_RELU>{}) \
-                            : fn(std::integral_constant<int, A1>{}, std::integral_constant<int, ACT_IDENTITY>{})
-    switch (act1) {
-        case ACT_IDENTITY: SIR_ACT2(ACT_IDENTITY);
-        case ACT_RELU: SIR_ACT2(ACT_RELU);
-        case ACT_LEAKY: SIR_ACT2(ACT_LEAKY);
-        case ACT_GELU: SIR_ACT2(ACT_GELU);
-        default: SIR_ACT2(ACT_GELU_TANH);
-    }
-#undef SIR_ACT2
+    return by_act<ACTS_ALL>(act1, [&](auto a1) {
+        return act2 == ACT_RELU ? fn(a1, std::integral_constant<int, ACT_RELU>{})
+                                : fn(a1, std::integral_constant<int, ACT_IDENTITY>{});
+    });
 }
 
 }  // namespace

@@ -337,7 +337,6 @@ bool eshape(int H, int* lpr, int* nv) {
     return true;
 }
 
-bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <int ACT, int AGG, int LPR, int NV>
 hipError_t launch_fwd_t(const EEdgeArgs& a, hipStream_t st) {
@@ -418,8 +417,8 @@ hipError_t run_eedge_fwd(const EEdgeArgs& a, int agg, int act, hipStream_t st, c
         *why = "the edge-term forward needs H % 4 == 0 and 4 <= H <= 1024";
         return hipErrorInvalidValue;
     }
-    if (!(al16(a.Q) && al16(a.K) && al16(a.Eh) && al16(a.S) && al16(a.partial) && a.ldq % 4 == 0 && a.ldk % 4 == 0 &&
-          a.lde % 4 == 0 && a.lds % 4 == 0)) {
+    if (!(aligned16(a.Q) && aligned16(a.K) && aligned16(a.Eh) && aligned16(a.S) && aligned16(a.partial) &&
+          a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.lde % 4 == 0 && a.lds % 4 == 0)) {
         *why = "the edge-term forward needs 16-B aligned rows (aligned pointers, leading dimensions multiples of 4)";
         return hipErrorInvalidValue;
     }
@@ -443,7 +442,7 @@ hipError_t run_eedge_bwd_e(const EEdgeArgs& a, int agg, int act, hipStream_t st,
         *why = "the edge-term backward needs H % 4 == 0 and 4 <= H <= 1024";
         return hipErrorInvalidValue;
     }
-    if (!(al16(a.G) && al16(a.dE) && a.ldg % 4 == 0 && a.ldde % 4 == 0)) {
+    if (!(aligned16(a.G) && aligned16(a.dE) && a.ldg % 4 == 0 && a.ldde % 4 == 0)) {
         *why = "the edge-term backward needs 16-B aligned rows (aligned pointers, leading dimensions multiples of 4)";
         return hipErrorInvalidValue;
     }

@@ -1606,7 +1606,6 @@ static bool nt_2b_auto(int K, int N) {
 #ifndef SIR_LT_BLOCKS
 #define SIR_LT_BLOCKS 512       // k_gemm_lt TN: row splits until about this many blocks
 #endif
-static bool aligned16(const void* p, int64_t ld) { return ((uintptr_t)p & 15u) == 0 && ld % 4 == 0; }
 // TN row splits of k_gemm_lt: each split a multiple of KS rows, at most 32 splits
 static int gemm_tn_splits_lt(int64_t R, int64_t tiles, int KS, int64_t* rps) {
     int64_t P = (SIR_LT_BLOCKS + tiles - 1) / tiles;
@@ -1685,8 +1684,8 @@ hipError_t run_gemm_nt_direct(const float* A, int64_t lda, int64_t M, int K, con
     if (lt < 0) lt = nt_lt_auto(M, N);
     const NtW w{W, ldw, W2, ldw2, W2 != nullptr ? split : INT64_MAX, bias_cols};
     // k_gemm_lt: 16-byte loads of both operands (and of W2), every byte offset of a tile's resource in 31 bits
-    if (lt > 0 && K % 4 == 0 && N % 4 == 0 && aligned16(A, lda) && aligned16(W, ldw) && ((uintptr_t)bias & 15u) == 0
-        && (W2 == nullptr || aligned16(W2, ldw2)) && 128 * lda < ((int64_t)1 << 29)
+    if (lt > 0 && K % 4 == 0 && N % 4 == 0 && aligned16(A) && lda % 4 == 0 && aligned16(W) && ldw % 4 == 0
+        && aligned16(bias) && (W2 == nullptr || (aligned16(W2) && ldw2 % 4 == 0)) && 128 * lda < ((int64_t)1 << 29)
         && (trans ? (int64_t)K * ldw : 128 * ldw) < ((int64_t)1 << 29)
         && (M + 31) / 32 * ((N + 31) / 32) < ((int64_t)1 << 31)) {
         switch (lt * 2 + (trans ? 1 : 0)) {
@@ -1885,7 +1884,8 @@ hipError_t run_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb,
     float* part = static_cast<float*>(workspace);
     float* cpart = colsum != nullptr ? part + (int64_t)P * Mc * Nc : nullptr;
     const int lt = lt_env("SIR_LT_TN", SIR_LT_TN);
-    if (small && lt > 0 && lt <= 5 && aligned16(A, lda) && aligned16(B, ldb) && (Mc + 31) / 32 * ((Nc + 31) / 32) < (1 << 24)) {
+    if (small && lt > 0 && lt <= 5 && aligned16(A) && lda % 4 == 0 && aligned16(B) && ldb % 4 == 0 &&
+        (Mc + 31) / 32 * ((Nc + 31) / 32) < (1 << 24)) {
         switch (lt) {
         case 1: launch_tn_lt<2, 2, 1>(A, lda, B, ldb, R, Mc, Nc, part, colsum != nullptr, st); break;
         case 2: launch_tn_lt<1, 2, 2>(A, lda, B, ldb, R, Mc, Nc, part, colsum != nullptr, st); break;

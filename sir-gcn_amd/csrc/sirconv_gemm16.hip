@@ -20,6 +20,7 @@
 // (sirconv_gemm.hip): deterministic.
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_device.h"
 #include "sirconv_gemm_util.h"
 #include "sirconv_dropout.h"
 
@@ -544,16 +545,11 @@ k_dropout_apply(void* __restrict__ X, int64_t ldx, int64_t M, int N, Drop drop) 
     const uint32_t rh = drop_row_hash(drop, m);
     for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) {
         const bool k = drop_keep(drop, rh, drop.col0 + n);
-        if constexpr (DT == SIR_DTYPE_F32) {
-            float* p = static_cast<float*>(X) + m * ldx + n;
-            *p = k ? *p * drop.scale : 0.f;
-        } else if constexpr (DT == SIR_DTYPE_BF16) {
-            __bf16* p = static_cast<__bf16*>(X) + m * ldx + n;
-            *p = k ? (__bf16)((float)*p * drop.scale) : (__bf16)0.f;
-        } else {
-            _Float16* p = static_cast<_Float16*>(X) + m * ldx + n;
-            *p = k ? (_Float16)((float)*p * drop.scale) : (_Float16)0.f;
-        }
+        typename Stor<DT>::T* p = static_cast<typename Stor<DT>::T*>(X) + m * ldx + n;
+        float v[1];
+        tload_p<DT, 1>(v, p);
+        v[0] = k ? v[0] * drop.scale : 0.f;
+        tstore_p<DT, 1>(p, v);
     }
 }
 }  // namespace
@@ -562,10 +558,10 @@ hipError_t run_dropout_apply(void* X, int64_t ldx, int64_t M, int N, int dtype, 
     if (M == 0 || N == 0 || !drop.on()) return hipSuccess;
     if (M > 2147483647) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((N + 255) / 256 < 4 ? (N + 255) / 256 : 4), (unsigned)M);
-    if (dtype == SIR_DTYPE_F32) hipLaunchKernelGGL(k_dropout_apply<SIR_DTYPE_F32>, grid, dim3(256), 0, st, X, ldx, M, N, drop);
-    else if (dtype == SIR_DTYPE_BF16) hipLaunchKernelGGL(k_dropout_apply<SIR_DTYPE_BF16>, grid, dim3(256), 0, st, X, ldx, M, N, drop);
-    else hipLaunchKernelGGL(k_dropout_apply<SIR_DTYPE_F16>, grid, dim3(256), 0, st, X, ldx, M, N, drop);
-    return hipGetLastError();
+    return by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_dropout_apply<dt()>, grid, dim3(256), 0, st, X, ldx, M, N, drop);
+        return hipGetLastError();
+    });
 }
 
 int64_t gemm_pack16_bytes(int64_t N, int64_t K) { return (N + 255) / 256 * 256 * K * 2; }

@@ -360,13 +360,13 @@ void gdispatch(GShape s, Fn&& fn) {
     }
 }
 
-bool al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
 hipError_t run_gather_add(const GenericArgs& a, hipStream_t st, int act, float slope, uint64_t* smask) {
     GShape s;
-    const bool v4 = al16(a.X) && al16(a.X2) && al16(a.out) && a.ldx % 4 == 0 && a.ldx2 % 4 == 0 && a.ldo % 4 == 0;
+    const bool v4 = aligned16(a.X) && aligned16(a.X2) && aligned16(a.out) && a.ldx % 4 == 0 && a.ldx2 % 4 == 0 &&
+                    a.ldo % 4 == 0;
     if (!gshape(a.F, v4, &s)) return hipErrorInvalidValue;
     if (act != ACT_IDENTITY && act != ACT_RELU && act != ACT_LEAKY) return hipErrorInvalidValue;
     if (smask != nullptr && !(a.F == 256 && s.nv == 1 && s.vw == 4)) return hipErrorInvalidValue;
@@ -396,7 +396,7 @@ hipError_t run_gather_add(const GenericArgs& a, hipStream_t st, int act, float s
 
 hipError_t run_seg_sum(const GenericArgs& a, hipStream_t st) {
     GShape s;
-    const bool v4 = al16(a.X) && al16(a.out) && al16(a.partial) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
+    const bool v4 = aligned16(a.X) && aligned16(a.out) && aligned16(a.partial) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
     if (!gshape(a.F, v4, &s)) return hipErrorInvalidValue;
     if (a.n_items == 0) return hipSuccess;
     gdispatch(s, [&](auto nv_, auto vw_) {
@@ -418,7 +418,7 @@ hipError_t run_seg_sum(const GenericArgs& a, hipStream_t st) {
 
 hipError_t run_edge_bcast(const GenericArgs& a, hipStream_t st) {
     GShape s;
-    const bool v4 = al16(a.X) && al16(a.out) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
+    const bool v4 = aligned16(a.X) && aligned16(a.out) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
     if (!gshape(a.F, v4, &s)) return hipErrorInvalidValue;
     if (a.n_items == 0) return hipSuccess;
     gdispatch(s, [&](auto nv_, auto vw_) {
@@ -432,7 +432,7 @@ hipError_t run_edge_bcast(const GenericArgs& a, hipStream_t st) {
 
 hipError_t run_seg_max(const GenericArgs& a, hipStream_t st) {
     GShape s;
-    const bool v4 = al16(a.X) && al16(a.out) && al16(a.partial) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
+    const bool v4 = aligned16(a.X) && aligned16(a.out) && aligned16(a.partial) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
     if (!gshape(a.F, v4, &s)) return hipErrorInvalidValue;
     if (a.n_items == 0) return hipSuccess;
     gdispatch(s, [&](auto nv_, auto vw_) {
@@ -451,7 +451,7 @@ hipError_t run_seg_max(const GenericArgs& a, hipStream_t st) {
 
 hipError_t run_seg_max_bwd(const GenericArgs& a, hipStream_t st) {
     GShape s;
-    const bool v4 = al16(a.X) && al16(a.out) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
+    const bool v4 = aligned16(a.X) && aligned16(a.out) && a.ldx % 4 == 0 && a.ldo % 4 == 0;
     if (!gshape(a.F, v4, &s)) return hipErrorInvalidValue;
     if (a.n_items == 0) return hipSuccess;
     gdispatch(s, [&](auto nv_, auto vw_) {

@@ -19,6 +19,7 @@
 
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_device.h"
 #include "sirconv_normdrop.h"
 
 namespace sir {
@@ -35,7 +36,7 @@ __device__ __forceinline__ void walk_rows(int64_t r0, int64_t r1, const float* _
     for (; i + RB <= r1; i += RB) {
         float v[RB][VW];
 #pragma unroll
-        for (int k = 0; k < RB; ++k) vld<VW>(v[k], base + (i + k) * ld + c * VW);
+        for (int k = 0; k < RB; ++k) vload<VW>(v[k], base + (i + k) * ld + c * VW);
 #pragma unroll
         for (int k = 0; k < RB; ++k) f(i + k, v[k]);
     }
@@ -43,7 +44,7 @@ __device__ __forceinline__ void walk_rows(int64_t r0, int64_t r1, const float* _
         const int n = (int)(r1 - i);
         float v[RB][VW];
 #pragma unroll
-        for (int k = 0; k < RB; ++k) vld<VW>(v[k], base + (i + (k < n ? k : 0)) * ld + c * VW);
+        for (int k = 0; k < RB; ++k) vload<VW>(v[k], base + (i + (k < n ? k : 0)) * ld + c * VW);
 #pragma unroll
         for (int k = 0; k < RB; ++k)
             if (k < n) f(i + k, v[k]);
@@ -58,8 +59,8 @@ __device__ __forceinline__ void walk_rows2(int64_t r0, int64_t r1, const float* 
         float u[RB][VW], v[RB][VW];
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
-            vld<VW>(u[k], a + (i + k) * lda + c * VW);
-            vld<VW>(v[k], b + (i + k) * ldb + c * VW);
+            vload<VW>(u[k], a + (i + k) * lda + c * VW);
+            vload<VW>(v[k], b + (i + k) * ldb + c * VW);
         }
 #pragma unroll
         for (int k = 0; k < RB; ++k) f(i + k, u[k], v[k]);
@@ -70,8 +71,8 @@ __device__ __forceinline__ void walk_rows2(int64_t r0, int64_t r1, const float* 
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
             const int64_t q = i + (k < n ? k : 0);
-            vld<VW>(u[k], a + q * lda + c * VW);
-            vld<VW>(v[k], b + q * ldb + c * VW);
+            vload<VW>(u[k], a + q * lda + c * VW);
+            vload<VW>(v[k], b + q * ldb + c * VW);
         }
 #pragma unroll
         for (int k = 0; k < RB; ++k)
@@ -101,9 +102,9 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
 #pragma unroll
         for (int x = 0; x < VW; ++x) s[x] += v[x];
     });
-    vld<VW>(wv, w + c * VW);
-    if (bias) vld<VW>(bv, bias + c * VW);
-    if (ms) vld<VW>(mv, ms + c * VW);
+    vload<VW>(wv, w + c * VW);
+    if (bias) vload<VW>(bv, bias + c * VW);
+    if (ms) vload<VW>(mv, ms + c * VW);
 #pragma unroll
     for (int x = 0; x < VW; ++x) {
         s[x] = (r1 > r0) ? s[x] / nf : 0.f;               // norm.py:21 mean
@@ -127,7 +128,7 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
             const float d = v[x] - t[x];
             y[x] = wv[x] * d / sd[x];
             if (bias) y[x] = y[x] + bv[x];
-            y[x] = norm_act<ACT>(y[x], slope);
+            y[x] = sig<ACT>(y[x], slope);
             if constexpr (DROP) y[x] = drop_keep(drop, rh, c * VW + x) ? y[x] * drop.scale : 0.f;
         }
     };
@@ -135,7 +136,7 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         walk_rows<VW>(r0, r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
             float y[VW];
             norm_row(i, v, y);
-            vst<VW>(Y + i * ldy + c * VW, y);
+            vstore<VW>(Y + i * ldy + c * VW, y);
         });
     } else {                                              // + resid (model.py:73)
         walk_rows2<VW>(r0, r1, X, ldx, R, ldr, c, [&](int64_t i, const float (&v)[VW], const float (&r)[VW]) {
@@ -143,11 +144,11 @@ k_gn_fwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
             norm_row(i, v, y);
 #pragma unroll
             for (int x = 0; x < VW; ++x) y[x] = y[x] + r[x];
-            vst<VW>(Y + i * ldy + c * VW, y);
+            vstore<VW>(Y + i * ldy + c * VW, y);
         });
     }
-    vst<VW>(mean_out + b * F + c * VW, s);
-    vst<VW>(std_out + b * F + c * VW, sd);
+    vstore<VW>(mean_out + b * F + c * VW, s);
+    vstore<VW>(std_out + b * F + c * VW, sd);
 }
 
 // ACT: dY is the gradient of act(y); the kernel takes g = act'(y) dY with y = the forward's norm output,
@@ -170,15 +171,15 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
     const int64_t r0 = off[b], r1 = off[b + 1];
     const float nf = (float)(r1 - r0);
     float wv[VW], mv[VW], mu[VW], sd[VW], t[VW], A[VW], G[VW], Bs[VW], bv[VW];
-    vld<VW>(wv, w + c * VW);
-    if (ACT != SIR_ACT_IDENTITY && bias != nullptr) vld<VW>(bv, bias + c * VW);
-    if (ms) vld<VW>(mv, ms + c * VW);
+    vload<VW>(wv, w + c * VW);
+    if (ACT != SIR_ACT_IDENTITY && bias != nullptr) vload<VW>(bv, bias + c * VW);
+    if (ms) vload<VW>(mv, ms + c * VW);
     else {
 #pragma unroll
         for (int x = 0; x < VW; ++x) mv[x] = 1.f;
     }
-    vld<VW>(mu, mean + b * F + c * VW);
-    vld<VW>(sd, sdv + b * F + c * VW);
+    vload<VW>(mu, mean + b * F + c * VW);
+    vload<VW>(sd, sdv + b * F + c * VW);
 #pragma unroll
     for (int x = 0; x < VW; ++x) { t[x] = ms ? mu[x] * mv[x] : mu[x]; A[x] = 0.f; G[x] = 0.f; Bs[x] = 0.f; }
     // act'(y) dY for the row (y: the forward's norm output, same ops)
@@ -194,7 +195,7 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
             } else {
                 float y = wv[x] * (v[x] - t[x]) / sd[x];
                 if (bias) y = y + bv[x];
-                g[x] = norm_act_bwd<ACT>(y, g0, slope);
+                g[x] = dsig<ACT>(y, g0, slope);
             }
         }
     };
@@ -222,7 +223,7 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         float o[VW];
 #pragma unroll
         for (int x = 0; x < VW; ++x) o[x] = (k1[x] * g[x] - k2[x] * (v[x] - t[x])) - mv[x] * Bs[x] / nf;
-        vst<VW>(dX + i * lddx + c * VW, o);
+        vstore<VW>(dX + i * lddx + c * VW, o);
     });
     float pw[VW], pm[VW];
 #pragma unroll
@@ -230,9 +231,9 @@ k_gn_bwd(const int64_t* __restrict__ off, int64_t B, int F, int n_cc,
         pw[x] = (r1 > r0) ? A[x] / sd[x] : 0.f;
         pm[x] = -(mu[x] * Bs[x]);
     }
-    vst<VW>(dw_part + b * F + c * VW, pw);
-    if (dms_part) vst<VW>(dms_part + b * F + c * VW, pm);
-    vst<VW>(db_part + b * F + c * VW, G);
+    vstore<VW>(dw_part + b * F + c * VW, pw);
+    if (dms_part) vstore<VW>(dms_part + b * F + c * VW, pm);
+    vstore<VW>(db_part + b * F + c * VW, G);
 }
 
 // One column per lane (VW 1) by default: a wave walks its graph's rows in order three times, so
@@ -252,8 +253,9 @@ hipError_t run_graph_norm_fwd(const int64_t* off, int64_t B, int F, const float*
                               int64_t ldr, float* Y, int64_t ldy, float* mean, float* sd, const Drop& drop,
                               hipStream_t st) {
     if (B == 0) return hipSuccess;
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
-                    al(R) && al(w) && al(bias) && al(ms) && al(mean) && al(sd) && gn_wide(B, F);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && aligned16(X) &&
+                    aligned16(Y) && aligned16(R) && aligned16(w) && aligned16(bias) && aligned16(ms) &&
+                    aligned16(mean) && aligned16(sd) && gn_wide(B, F);
     const int n_cc = (F / (v4 ? 4 : 1) + 63) / 64;
     const unsigned blocks = (unsigned)(B * n_cc);
     return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
@@ -267,9 +269,9 @@ hipError_t run_graph_norm_bwd(const int64_t* off, int64_t B, int F, const float*
                               const float* sd, int act, float slope, float* dX, int64_t lddx, float* dw_part,
                               float* dms_part, float* db_part, const Drop& drop, hipStream_t st) {
     if (B == 0) return hipSuccess;
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && al(X) && al(dY) && al(dX) &&
-                    al(w) && al(bias) && al(ms) && al(mean) && al(sd) && al(dw_part) && al(dms_part) && al(db_part) &&
-                    gn_wide(B, F);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && aligned16(X) && aligned16(dY) &&
+                    aligned16(dX) && aligned16(w) && aligned16(bias) && aligned16(ms) && aligned16(mean) &&
+                    aligned16(sd) && aligned16(dw_part) && aligned16(dms_part) && aligned16(db_part) && gn_wide(B, F);
     const int n_cc = (F / (v4 ? 4 : 1) + 63) / 64;
     const unsigned blocks = (unsigned)(B * n_cc);
     return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "sirconv_dropout.h"
 
 namespace sir {
@@ -317,6 +319,51 @@ inline int device_cu_count() {
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
     if (dev < 64) cached[dev] = ncu;
     return ncu;
+}
+
+// ------------------------------------------------------------------------------ host: choosing an instantiation
+// by_act<ACTS>(act, f): f(std::integral_constant<int, ACT_*>()) for an activation code of the first ACTS codes,
+// f's hipError_t; any other code: hipErrorInvalidValue, f not called.  ACTS_ALL: the conv kernels and the
+// pre-norm tail; ACTS_NORM (identity, ReLU, LeakyReLU): the norm and residual passes.
+enum { ACTS_NORM = 3, ACTS_ALL = 5 };
+template <int ACTS, typename Fn>
+hipError_t by_act(int act, Fn&& f) {
+    static_assert(ACTS == ACTS_NORM || ACTS == ACTS_ALL, "a set of activations");
+    if (act < 0 || act >= ACTS) return hipErrorInvalidValue;
+    switch (act) {
+        case ACT_IDENTITY: return f(std::integral_constant<int, ACT_IDENTITY>());
+        case ACT_RELU: return f(std::integral_constant<int, ACT_RELU>());
+        case ACT_LEAKY: return f(std::integral_constant<int, ACT_LEAKY>());
+    }
+    if constexpr (ACTS == ACTS_ALL) {
+        if (act == ACT_GELU) return f(std::integral_constant<int, ACT_GELU>());
+        return f(std::integral_constant<int, ACT_GELU_TANH>());
+    }
+    return hipErrorInvalidValue;
+}
+// by_dtype(dtype, f): the same over the storage dtype, f(std::integral_constant<int, ST_*>())
+template <typename Fn>
+hipError_t by_dtype(int dtype, Fn&& f) {
+    switch (dtype) {
+        case ST_F32: return f(std::integral_constant<int, ST_F32>());
+        case ST_BF16: return f(std::integral_constant<int, ST_BF16>());
+        case ST_F16: return f(std::integral_constant<int, ST_F16>());
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// p may be accessed in vectors of `bytes` (a power of two) / of 16 bytes.  NULL, an operand that is not there,
+// passes (it is address 0): a caller that needs the operand tests for NULL itself.
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+inline bool aligned16(const void* p) { return aligned_to(p, 16); }
+
+// grid of a streaming pass over [M, N] in groups of 4 elements, one per thread of a 256-thread block, grid-stride:
+// one block per 256 groups, at most 8 per CU
+inline unsigned stream_grid(int64_t M, int N) {
+    const int64_t q = M * (N / 4);
+    const int64_t b = (q + 255) / 256;
+    const int64_t cap = 8 * (int64_t)device_cu_count();
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
 }  // namespace sir

@@ -158,7 +158,6 @@ k_label_prop_combine(LabelPropArgs a) {
     }
 }
 
-bool lp_al16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <int L, int VW>
 void lp_launch(const LabelPropArgs& a, dim3 grid, hipStream_t st) {
@@ -191,8 +190,8 @@ hipError_t lp_dispatch(const LabelPropArgs& a, hipStream_t st) {
 hipError_t run_label_prop(const LabelPropArgs& a, hipStream_t st) {
     if (a.V == 0 || a.n_items == 0) return hipSuccess;
     const bool v4 = a.F % 4 == 0 && a.ldy % 4 == 0 && a.ldy0 % 4 == 0 && a.ldo % 4 == 0 &&
-                    (a.post != SIR_LP_POST_FIX || a.ldf % 4 == 0) && lp_al16(a.Y) && lp_al16(a.Y0) &&
-                    lp_al16(a.out) && lp_al16(a.partial) && (a.post != SIR_LP_POST_FIX || lp_al16(a.Yfix));
+                    (a.post != SIR_LP_POST_FIX || a.ldf % 4 == 0) && aligned16(a.Y) && aligned16(a.Y0) &&
+                    aligned16(a.out) && aligned16(a.partial) && (a.post != SIR_LP_POST_FIX || aligned16(a.Yfix));
     hipError_t err = v4 ? lp_dispatch<4>(a, st) : lp_dispatch<1>(a, st);
     if (err != hipSuccess || a.n_splits == 0) return err;
     hipLaunchKernelGGL(k_label_prop_combine, dim3((unsigned)a.n_splits), dim3(256), 0, st, a);

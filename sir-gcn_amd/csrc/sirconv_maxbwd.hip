@@ -709,18 +709,6 @@ done:
 #define SIR_MAXB_U 4
 #endif
 
-template <typename Fn>
-hipError_t maxb_acts(int act1, Fn&& fn) {
-    switch (act1) {
-        case ACT_IDENTITY: return fn(std::integral_constant<int, ACT_IDENTITY>());
-        case ACT_RELU: return fn(std::integral_constant<int, ACT_RELU>());
-        case ACT_LEAKY: return fn(std::integral_constant<int, ACT_LEAKY>());
-        case ACT_GELU: return fn(std::integral_constant<int, ACT_GELU>());
-        case ACT_GELU_TANH: return fn(std::integral_constant<int, ACT_GELU_TANH>());
-        default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 int64_t maxb_dw_ranges(int64_t V) {
@@ -757,7 +745,7 @@ hipError_t run_max_dw_qk(const int* rowptr, const int* col, int64_t V, const int
     if (V == 0) return wpart != nullptr ? hipMemsetAsync(wpart, 0, (size_t)ldw * sizeof(float), st) : hipSuccess;
     const int64_t R = max_dw_rows_ranges(V, H);
     const int rows_per = (int)((V + R - 1) / R);
-    return maxb_acts(act1, [&](auto A1) -> hipError_t {
+    return by_act<ACTS_ALL>(act1, [&](auto A1) -> hipError_t {
         constexpr int X1 = decltype(A1)::value;
         hipLaunchKernelGGL((k_max_dw_qk2<X1>), dim3((unsigned)((H + 63) / 64), (unsigned)R), dim3(512), 0, st, rowptr,
                            col, arg, lda, dY, ldy, Q, ldq, K, ldk, (int)V, O, H, slope, rows_per, wpart, ldw);
@@ -800,7 +788,7 @@ hipError_t run_max_bwd_sparse(const MaxBwdArgs& a, hipStream_t st) {
     const int nsl = (H + 127) / 128;
     const int ncu = device_cu_count();
     const int nbs = (ncu + nsl - 1) / nsl;
-    err = maxb_acts(a.act1, [&](auto A1) -> hipError_t {
+    err = by_act<ACTS_ALL>(a.act1, [&](auto A1) -> hipError_t {
         constexpr int X1 = decltype(A1)::value;
         auto dz = [&](auto D, auto OP) -> hipError_t {
             constexpr bool DV = decltype(D)::value;

@@ -37,6 +37,7 @@
 
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_device.h"
 #include "sirconv_normdrop.h"
 
 namespace sir {
@@ -92,7 +93,7 @@ k_bn_stats(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
             const int64_t left = (r1 - base + rs - 1) / rs;       // this thread's rows from `base` on
             const int nb = left < 8 ? (int)left : 8;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) vld<VW>(v[k], X + (base + (int64_t)(k < nb ? k : 0) * rs) * ldx + (int64_t)p.c * VW);
+            for (int k = 0; k < 8; ++k) vload<VW>(v[k], X + (base + (int64_t)(k < nb ? k : 0) * rs) * ldx + (int64_t)p.c * VW);
             const double nbf = (double)nb;
             double n2 = na;
 #pragma unroll
@@ -243,8 +244,8 @@ k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int64_t row = base + (int64_t)k * rs < r1 ? base + (int64_t)k * rs : base;
-            vld<VW>(v[k], X + row * ldx + col);
-            if (R != nullptr) vld<VW>(r[k], R + row * ldr + col);
+            vload<VW>(v[k], X + row * ldx + col);
+            if (R != nullptr) vload<VW>(r[k], R + row * ldr + col);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -256,11 +257,11 @@ k_bn_apply(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int cwv, 
 #pragma unroll
                 for (int x = 0; x < VW; ++x) {
                     const float y = (float)(((double)v[k][x] - mu[x]) * a[x] + b[x]);
-                    o[x] = norm_act<ACT>(y, slope);
+                    o[x] = sig<ACT>(y, slope);
                     if constexpr (DROP) o[x] = drop_keep(drop, rh, (int)col + x) ? o[x] * drop.scale : 0.f;
                     if (R != nullptr) o[x] = o[x] + r[k][x];
                 }
-                vst<VW>(Y + row * ldy + col, o);
+                vstore<VW>(Y + row * ldy + col, o);
             }
         }
     }
@@ -291,8 +292,8 @@ k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int64_t row = base + (int64_t)k * rs < r1 ? base + (int64_t)k * rs : base;
-                vld<VW>(v[k], X + row * ldx + col);
-                vld<VW>(d[k], D + row * ldg + col);
+                vload<VW>(v[k], X + row * ldx + col);
+                vload<VW>(d[k], D + row * ldg + col);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -305,7 +306,7 @@ k_bn_bwd_red(const float* __restrict__ X, int64_t ldx, const float* __restrict__
                         const float y = (float)(c * a[x] + b[x]);
                         float g0 = d[k][x];
                         if constexpr (DROP) g0 = drop_keep(drop, rh, (int)col + x) ? g0 * drop.scale : 0.f;
-                        const float gg = norm_act_bwd<ACT>(y, g0, slope);
+                        const float gg = dsig<ACT>(y, g0, slope);
                         sb[x] += (double)gg;
                         sg[x] += (double)gg * c;
                     }
@@ -357,8 +358,8 @@ k_bn_bwd_app(const float* __restrict__ X, int64_t ldx, const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int64_t row = base + (int64_t)k * rs < r1 ? base + (int64_t)k * rs : base;
-            vld<VW>(v[k], X + row * ldx + col);
-            vld<VW>(d[k], D + row * ldg + col);
+            vload<VW>(v[k], X + row * ldx + col);
+            vload<VW>(d[k], D + row * ldg + col);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -373,10 +374,10 @@ k_bn_bwd_app(const float* __restrict__ X, int64_t ldx, const float* __restrict__
                     const float y = (float)(c * a[x] + b[x]);
                     float g0 = d[k][x];
                     if constexpr (DROP) g0 = drop_keep(drop, rh, (int)col + x) ? g0 * drop.scale : 0.f;
-                    const float gg = norm_act_bwd<ACT>(y, g0, slope);
+                    const float gg = dsig<ACT>(y, g0, slope);
                     o[x] = (float)((((double)gg - gm[x]) - c * kk[x]) * a[x]);
                 }
-                vst<VW>(dX + row * lddx + col, o);
+                vstore<VW>(dX + row * lddx + col, o);
             }
         }
     }
@@ -414,7 +415,7 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
         on[j] = c < N;
 #pragma unroll
         for (int x = 0; x < VW; ++x) { g[j][x] = 0.f; b[j][x] = 0.f; }
-        if (on[j]) { vld<VW>(g[j], gamma + c); vld<VW>(b[j], beta + c); }
+        if (on[j]) { vload<VW>(g[j], gamma + c); vload<VW>(b[j], beta + c); }
     }
     for (int64_t r = r0; r < r1; r += RB) {
         float v[RB][NCH][VW], rr[RB][NCH][VW];
@@ -426,8 +427,8 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
 #pragma unroll
                 for (int x = 0; x < VW; ++x) { v[k][j][x] = 0.f; rr[k][j][x] = 0.f; }
                 if (on[j]) {
-                    vld<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
-                    if (R != nullptr) vld<VW>(rr[k][j], R + row * ldr + (j * 64 + lane) * VW);
+                    vload<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
+                    if (R != nullptr) vload<VW>(rr[k][j], R + row * ldr + (j * 64 + lane) * VW);
                 }
             }
         }
@@ -458,12 +459,12 @@ k_ln_fwd(const float* __restrict__ X, int64_t ldx, int64_t M, int N, int64_t rpw
 #pragma unroll
                         for (int x = 0; x < VW; ++x) {
                             const float y = (v[k][j][x] - mu) * rstd * g[j][x] + b[j][x];
-                            o[x] = norm_act<ACT>(y, slope);
+                            o[x] = sig<ACT>(y, slope);
                             if constexpr (DROP)
                                 o[x] = drop_keep(drop, rh, (j * 64 + lane) * VW + x) ? o[x] * drop.scale : 0.f;
                             if (R != nullptr) o[x] = o[x] + rr[k][j][x];
                         }
-                        vst<VW>(Y + (r + k) * ldy + (j * 64 + lane) * VW, o);
+                        vstore<VW>(Y + (r + k) * ldy + (j * 64 + lane) * VW, o);
                     }
                 }
                 if (lane == 0) { mean_out[r + k] = mu; rstd_out[r + k] = rstd; }
@@ -492,7 +493,7 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
         on[j] = c < N;
 #pragma unroll
         for (int x = 0; x < VW; ++x) { g[j][x] = 0.f; b[j][x] = 0.f; dw[j][x] = 0.f; db[j][x] = 0.f; }
-        if (on[j]) { vld<VW>(g[j], gamma + c); vld<VW>(b[j], beta + c); }
+        if (on[j]) { vload<VW>(g[j], gamma + c); vload<VW>(b[j], beta + c); }
     }
     for (int64_t r = r0; r < r1; r += RB) {
         float v[RB][NCH][VW], d[RB][NCH][VW], mu[RB], rs[RB];
@@ -506,8 +507,8 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
 #pragma unroll
                 for (int x = 0; x < VW; ++x) { v[k][j][x] = 0.f; d[k][j][x] = 0.f; }
                 if (on[j]) {
-                    vld<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
-                    vld<VW>(d[k][j], D + row * ldg + (j * 64 + lane) * VW);
+                    vload<VW>(v[k][j], X + row * ldx + (j * 64 + lane) * VW);
+                    vload<VW>(d[k][j], D + row * ldg + (j * 64 + lane) * VW);
                 }
             }
         }
@@ -526,7 +527,7 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
                         const float y = xh[j][x] * g[j][x] + b[j][x];
                         float g0 = d[k][j][x];
                         if constexpr (DROP) g0 = drop_keep(drop, rh, (j * 64 + lane) * VW + x) ? g0 * drop.scale : 0.f;
-                        const float gg = on[j] ? norm_act_bwd<ACT>(y, g0, slope) : 0.f;
+                        const float gg = on[j] ? dsig<ACT>(y, g0, slope) : 0.f;
                         db[j][x] += gg;
                         dw[j][x] += gg * xh[j][x];
                         a[j][x] = gg * g[j][x];
@@ -542,7 +543,7 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
                         float o[VW];
 #pragma unroll
                         for (int x = 0; x < VW; ++x) o[x] = rs[k] * ((a[j][x] - m1) - xh[j][x] * m2);
-                        vst<VW>(dX + (r + k) * lddx + (j * 64 + lane) * VW, o);
+                        vstore<VW>(dX + (r + k) * lddx + (j * 64 + lane) * VW, o);
                     }
                 }
             }
@@ -551,8 +552,8 @@ k_ln_bwd(const float* __restrict__ X, int64_t ldx, const float* __restrict__ D, 
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
         if (on[j]) {
-            vst<VW>(dw_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, dw[j]);
-            vst<VW>(db_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, db[j]);
+            vstore<VW>(dw_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, dw[j]);
+            vstore<VW>(db_part + (int64_t)blockIdx.x * ldp + (j * 64 + lane) * VW, db[j]);
         }
     }
 }
@@ -588,7 +589,7 @@ hipError_t run_batch_norm_stats(const float* X, int64_t ldx, int64_t M, int N, f
     const int64_t S = batch_norm_slabs(M);
     double* pmean = reinterpret_cast<double*>(work);
     double* pm2 = pmean + S * N;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && al(X);
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && aligned16(X);
     const BnGeom g = bn_geom(M, N, v4);
     if (v4)
         hipLaunchKernelGGL((k_bn_stats<4>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv, g.rs, pmean, pm2);
@@ -604,8 +605,8 @@ hipError_t run_batch_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N,
                                   const float* R, int64_t ldr, float* Y, int64_t ldy, const Drop& drop,
                                   hipStream_t st) {
     if (M == 0) return hipSuccess;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
-                    al(R);
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && aligned16(X) &&
+                    aligned16(Y) && aligned16(R);
     const BnGeom g = bn_geom(M, N, v4);
     return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
         hipLaunchKernelGGL((k_bn_apply<vw(), a(), dropped()>), g.grid, dim3(BN_THREADS), 0, st, X, ldx, M, N, g.cwv,
@@ -623,7 +624,8 @@ hipError_t run_batch_norm_act_bwd(const float* X, int64_t ldx, const float* D, i
     double* pdg = pdb + S * N;
     double* gmean = pdg + S * N;
     double* kdot = gmean + N;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && al(X) && al(D) && al(dX);
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && aligned16(X) && aligned16(D) &&
+                    aligned16(dX);
     const BnGeom g = bn_geom(M, N, v4);
     return by_drop(drop, [&](auto dropped, const Drop& d) {
         const hipError_t err = by_act_vw(act, v4, [&](auto a, auto vw) {
@@ -676,8 +678,8 @@ hipError_t run_layer_norm_act_fwd(const float* X, int64_t ldx, int64_t M, int N,
                                   const float* beta, float eps, int act, float slope, const float* R, int64_t ldr,
                                   float* Y, int64_t ldy, float* mean, float* rstd, const Drop& drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && al(X) && al(Y) &&
-                    al(R) && al(gamma) && al(beta);
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (R == nullptr || ldr % 4 == 0) && aligned16(X) &&
+                    aligned16(Y) && aligned16(R) && aligned16(gamma) && aligned16(beta);
     const int64_t rpw = layer_norm_rows_per_part(M);
     const unsigned blocks = (unsigned)layer_norm_parts(M);
     return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {
@@ -693,8 +695,9 @@ hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, i
                                   int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
                                   int64_t ldp, const Drop& drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
-    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && ldp % 4 == 0 && al(X) && al(D) &&
-                    al(dX) && al(gamma) && al(beta) && al(dw_part) && al(db_part);
+    const bool v4 = N % 4 == 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && ldp % 4 == 0 && aligned16(X) &&
+                    aligned16(D) && aligned16(dX) && aligned16(gamma) && aligned16(beta) && aligned16(dw_part) &&
+                    aligned16(db_part);
     const int64_t rpw = layer_norm_rows_per_part(M);
     const unsigned blocks = (unsigned)layer_norm_parts(M);
     return norm_dispatch(act, drop, v4, [&](auto a, auto dropped, auto vw, const Drop& d) {

@@ -1,6 +1,7 @@
 // sirconv_normdrop.h — the fused norm -> activation -> (dropout) -> + residual passes of GraphNorm
-// (sirconv_graphnorm.hip), BatchNorm and LayerNorm (sirconv_nodenorm.hip): their launchers, the device helpers
-// the kernels share and the host-side choice of a kernel instantiation.
+// (sirconv_graphnorm.hip), BatchNorm and LayerNorm (sirconv_nodenorm.hip): their launchers and the host-side
+// choice of a kernel instantiation.  The activation (sig / dsig) and the 1- or 4-float access (vload / vstore)
+// of the kernels are sirconv_device.h's.
 //
 // The layer dropout of the node-level models (ogbn-arxiv/model.py:49,70: norm -> act ->
 // dropout -> + resid; zinc/model.py:24,56: norm -> act -> dropout) fused into the three norm passes:
@@ -18,6 +19,7 @@
 #include <type_traits>
 
 #include "sirconv.h"
+#include "sirconv_internal.h"
 #include "sirconv_dropout.h"
 
 namespace sir {
@@ -47,41 +49,6 @@ hipError_t run_layer_norm_act_bwd(const float* X, int64_t ldx, const float* D, i
                                   int act, float slope, float* dX, int64_t lddx, float* dw_part, float* db_part,
                                   int64_t ldp, const Drop& drop, hipStream_t st);
 
-// VW floats at p: one 16-byte access (VW 4, p 16-B aligned) or one float
-template <int VW>
-__device__ __forceinline__ void vld(float (&d)[VW], const float* __restrict__ p) {
-    if constexpr (VW == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-    } else {
-        d[0] = p[0];
-    }
-}
-
-template <int VW>
-__device__ __forceinline__ void vst(float* __restrict__ p, const float (&s)[VW]) {
-    if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]);
-    else p[0] = s[0];
-}
-
-// the stack's activation after the norm (ogbn-arxiv/model.py:65-73: h = act(norm(h)) + resid), the
-// ops of torch's relu / leaky_relu and their backward (x > 0 ? g : 0 / g * slope)
-template <int ACT>
-__device__ __forceinline__ float norm_act(float y, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y <= 0.f ? 0.f : y;         // ReLU(NaN) = NaN, as torch.relu
-    else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? y : y * slope;
-    else return y;
-}
-template <int ACT>
-__device__ __forceinline__ float norm_act_bwd(float y, float g, float slope) {
-    if constexpr (ACT == SIR_ACT_RELU) return y > 0.f ? g : 0.f;
-    else if constexpr (ACT == SIR_ACT_LEAKY_RELU) return y > 0.f ? g : g * slope;
-    else return g;
-}
-
-// host: p may be read in 16-byte vectors (NULL: an operand that is not there)
-inline bool al(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // host: the kernel instantiation of a pass, its template arguments handed to a generic lambda as
 // std::integral_constants (k<vw(), act(), dropped()>).
 // by_drop: f(DROP, d) with DROP = drop.on() and d = drop, or Drop() when drop is off; f's result.
@@ -94,17 +61,11 @@ auto by_drop(const Drop& drop, Fn&& f) {
 // hipErrorInvalidValue (nothing launched) for an activation the passes do not have.
 template <typename Fn>
 auto by_act_vw(int act, bool v4, Fn&& launch) {
-    auto by_vw = [&](auto a) {
+    return by_act<ACTS_NORM>(act, [&](auto a) {
         if (v4) launch(a, std::integral_constant<int, 4>());
         else launch(a, std::integral_constant<int, 1>());
-    };
-    switch (act) {
-    case SIR_ACT_IDENTITY: by_vw(std::integral_constant<int, SIR_ACT_IDENTITY>()); break;
-    case SIR_ACT_RELU: by_vw(std::integral_constant<int, SIR_ACT_RELU>()); break;
-    case SIR_ACT_LEAKY_RELU: by_vw(std::integral_constant<int, SIR_ACT_LEAKY_RELU>()); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 // both: launch(ACT, DROP, VW, d), for a pass that is one launch
 template <typename Fn>

@@ -22,50 +22,12 @@
 
 #include "sirconv.h"
 #include "sirconv_internal.h"
+#include "sirconv_device.h"
 
 namespace sir {
 namespace {
 
 constexpr int POOL_R = SIR_POOL_SLAB_ROWS;
-
-template <int DT>
-struct PElt;
-template <>
-struct PElt<SIR_DTYPE_F32> {
-    typedef float T;
-};
-template <>
-struct PElt<SIR_DTYPE_BF16> {
-    typedef __bf16 T;
-};
-template <>
-struct PElt<SIR_DTYPE_F16> {
-    typedef _Float16 T;
-};
-
-// VW consecutive elements of type T (VW 4: one 16-B / 8-B access), widened to / rounded once from fp32
-template <typename T, int VW>
-__device__ __forceinline__ void pld(float (&d)[VW], const T* __restrict__ p) {
-    if constexpr (VW == 4) {
-        typedef T T4 __attribute__((ext_vector_type(4)));
-        const T4 t = *reinterpret_cast<const T4*>(p);
-        d[0] = (float)t[0]; d[1] = (float)t[1]; d[2] = (float)t[2]; d[3] = (float)t[3];
-    } else {
-        d[0] = (float)p[0];
-    }
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void pst(T* __restrict__ p, const float (&s)[VW]) {
-    if constexpr (VW == 4) {
-        typedef T T4 __attribute__((ext_vector_type(4)));
-        T4 t;
-        t[0] = (T)s[0]; t[1] = (T)s[1]; t[2] = (T)s[2]; t[3] = (T)s[3];
-        *reinterpret_cast<T4*>(p) = t;
-    } else {
-        p[0] = (T)s[0];
-    }
-}
 
 template <int VW>
 __device__ __forceinline__ void pst_i(int* __restrict__ p, const int (&s)[VW]) {
@@ -75,14 +37,14 @@ __device__ __forceinline__ void pst_i(int* __restrict__ p, const int (&s)[VW]) {
 
 // Rows [r0, r1) in node order, RB rows' loads in flight at a time (sirconv_graphnorm.hip walk_rows, for
 // any storage type); f(i, v) is applied in row order.
-template <typename T, int VW, int RB = 32, typename Fn>
-__device__ __forceinline__ void pool_walk(int64_t r0, int64_t r1, const T* __restrict__ base, int64_t ld, int c,
-                                          Fn f) {
+template <int DT, int VW, int RB = 32, typename Fn>
+__device__ __forceinline__ void pool_walk(int64_t r0, int64_t r1, const typename Stor<DT>::T* __restrict__ base,
+                                          int64_t ld, int c, Fn f) {
     int64_t i = r0;
     for (; i + RB <= r1; i += RB) {
         float v[RB][VW];
 #pragma unroll
-        for (int k = 0; k < RB; ++k) pld<T, VW>(v[k], base + (i + k) * ld + c * VW);
+        for (int k = 0; k < RB; ++k) tload_p<DT, VW>(v[k], base + (i + k) * ld + c * VW);
 #pragma unroll
         for (int k = 0; k < RB; ++k) f(i + k, v[k]);
     }
@@ -90,7 +52,7 @@ __device__ __forceinline__ void pool_walk(int64_t r0, int64_t r1, const T* __res
         const int n = (int)(r1 - i);
         float v[RB][VW];
 #pragma unroll
-        for (int k = 0; k < RB; ++k) pld<T, VW>(v[k], base + (i + (k < n ? k : 0)) * ld + c * VW);
+        for (int k = 0; k < RB; ++k) tload_p<DT, VW>(v[k], base + (i + (k < n ? k : 0)) * ld + c * VW);
 #pragma unroll
         for (int k = 0; k < RB; ++k)
             if (k < n) f(i + k, v[k]);
@@ -140,7 +102,7 @@ __global__ void __launch_bounds__(64)
 k_pool_fwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_cc, int64_t slots,
            const void* __restrict__ Xv, int64_t ldx, void* __restrict__ Pv, int64_t ldp, int* __restrict__ arg,
            float* __restrict__ work) {
-    typedef typename PElt<DT>::T T;
+    typedef typename Stor<DT>::T T;
     const T* __restrict__ X = static_cast<const T*>(Xv);
     T* __restrict__ P = static_cast<T*>(Pv);
     const int64_t t = (int64_t)blockIdx.x / n_cc;
@@ -158,17 +120,17 @@ k_pool_fwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_c
         // the slab's first row seeds (value, arg) whatever it holds — no "nothing seen yet" test in the walk —
         // and a later row replaces it in the maximum's order (max_beats: strict, so the first wins)
         if (s.r0 < s.r1) {
-            pld<T, VW>(acc, X + s.r0 * ldx + c * VW);
+            tload_p<DT, VW>(acc, X + s.r0 * ldx + c * VW);
 #pragma unroll
             for (int x = 0; x < VW; ++x) am[x] = (int)(s.r0 - s.g0);
         }
-        pool_walk<T, VW>(s.r0 + 1, s.r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
+        pool_walk<DT, VW>(s.r0 + 1, s.r1, X, ldx, c, [&](int64_t i, const float (&v)[VW]) {
 #pragma unroll
             for (int x = 0; x < VW; ++x)
                 if (max_beats(v[x], acc[x])) { acc[x] = v[x]; am[x] = (int)(i - s.g0); }
         });
     } else {
-        pool_walk<T, VW>(s.r0, s.r1, X, ldx, c, [&](int64_t, const float (&v)[VW]) {
+        pool_walk<DT, VW>(s.r0, s.r1, X, ldx, c, [&](int64_t, const float (&v)[VW]) {
 #pragma unroll
             for (int x = 0; x < VW; ++x) acc[x] += v[x];
         });
@@ -179,7 +141,7 @@ k_pool_fwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_c
 #pragma unroll
             for (int x = 0; x < VW; ++x) acc[x] = acc[x] / nf;
         }
-        pst<T, VW>(P + s.b * ldp + c * VW, acc);
+        tstore_p<DT, VW>(P + s.b * ldp + c * VW, acc);
         if constexpr (OP == SIR_POOL_MAX) pst_i<VW>(arg + s.b * F + c * VW, am);
     } else {
 #pragma unroll
@@ -197,7 +159,7 @@ template <int DT, int OP>
 __global__ void __launch_bounds__(256)
 k_pool_combine(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int64_t slots,
                const float* __restrict__ work, void* __restrict__ Pv, int64_t ldp, int* __restrict__ arg) {
-    typedef typename PElt<DT>::T T;
+    typedef typename Stor<DT>::T T;
     T* __restrict__ P = static_cast<T*>(Pv);
     const int* __restrict__ warg = reinterpret_cast<const int*>(work + slots * F);
     const int64_t total = B * F;
@@ -234,7 +196,7 @@ __global__ void __launch_bounds__(64)
 k_pool_bwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_cc, int64_t slots,
            const void* __restrict__ dPv, int64_t ldg, const int* __restrict__ arg, void* __restrict__ dXv,
            int64_t lddx) {
-    typedef typename PElt<DT>::T T;
+    typedef typename Stor<DT>::T T;
     const T* __restrict__ dP = static_cast<const T*>(dPv);
     T* __restrict__ dX = static_cast<T*>(dXv);
     const int64_t t = (int64_t)blockIdx.x / n_cc;
@@ -245,7 +207,7 @@ k_pool_bwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_c
     const int c = cc * 64 + (threadIdx.x & 63);
     if (c * VW >= F) return;
     float g[VW];
-    pld<T, VW>(g, dP + s.b * ldg + c * VW);
+    tload_p<DT, VW>(g, dP + s.b * ldg + c * VW);
     if constexpr (OP == SIR_POOL_MAX) {
         int am[VW];
         if constexpr (VW == 4) {
@@ -259,7 +221,7 @@ k_pool_bwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_c
             float o[VW];
 #pragma unroll
             for (int x = 0; x < VW; ++x) o[x] = am[x] == rel ? g[x] : 0.f;
-            pst<T, VW>(dX + i * lddx + c * VW, o);
+            tstore_p<DT, VW>(dX + i * lddx + c * VW, o);
         }
     } else {
         if constexpr (OP == SIR_POOL_MEAN) {
@@ -267,11 +229,9 @@ k_pool_bwd(const int64_t* __restrict__ off, int64_t B, int64_t V, int F, int n_c
 #pragma unroll
             for (int x = 0; x < VW; ++x) g[x] = g[x] / nf;
         }
-        for (int64_t i = s.r0; i < s.r1; ++i) pst<T, VW>(dX + i * lddx + c * VW, g);
+        for (int64_t i = s.r0; i < s.r1; ++i) tstore_p<DT, VW>(dX + i * lddx + c * VW, g);
     }
 }
-
-bool al_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 template <int DT, int VW>
 void launch_fwd(int op, unsigned blocks, hipStream_t st, const int64_t* off, int64_t B, int64_t V, int F, int n_cc,
@@ -329,47 +289,43 @@ hipError_t run_graph_pool_fwd(const int64_t* off, int64_t B, int64_t V, int F, i
                               int64_t ldx, void* P, int64_t ldp, int* arg, float* work, hipStream_t st) {
     if (B == 0) return hipSuccess;
     const uintptr_t vb = dtype == SIR_DTYPE_F32 ? 16 : 8;         // bytes of 4 elements
-    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldp % 4 == 0 && al_to(X, vb) && al_to(P, vb) && al_to(arg, 16);
+    const bool v4 = F % 4 == 0 && ldx % 4 == 0 && ldp % 4 == 0 && aligned_to(X, vb) && aligned_to(P, vb) &&
+                    aligned16(arg);
     const int vw = v4 ? 4 : 1;
     const int n_cc = (F / vw + 63) / 64;
     const int64_t slots = graph_pool_slots(V, B);
     if (slots * n_cc > 0x7fffffffLL) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)(slots * n_cc);
-#define SIR_POOL_FWD(DT_)                                                                                          \
-    if (v4) launch_fwd<DT_, 4>(op, blocks, st, off, B, V, F, n_cc, slots, X, ldx, P, ldp, arg, work);              \
-    else launch_fwd<DT_, 1>(op, blocks, st, off, B, V, F, n_cc, slots, X, ldx, P, ldp, arg, work);
-    if (dtype == SIR_DTYPE_F32) { SIR_POOL_FWD(SIR_DTYPE_F32) }
-    else if (dtype == SIR_DTYPE_BF16) { SIR_POOL_FWD(SIR_DTYPE_BF16) }
-    else { SIR_POOL_FWD(SIR_DTYPE_F16) }
-#undef SIR_POOL_FWD
-    hipError_t err = hipGetLastError();
+    hipError_t err = by_dtype(dtype, [&](auto dt) {
+        if (v4) launch_fwd<dt(), 4>(op, blocks, st, off, B, V, F, n_cc, slots, X, ldx, P, ldp, arg, work);
+        else launch_fwd<dt(), 1>(op, blocks, st, off, B, V, F, n_cc, slots, X, ldx, P, ldp, arg, work);
+        return hipGetLastError();
+    });
     if (err != hipSuccess || V <= POOL_R) return err;
     int64_t cb = (B * F + 255) / 256;
     const unsigned cblocks = (unsigned)(cb < 2048 ? cb : 2048);
-    if (dtype == SIR_DTYPE_F32) launch_combine<SIR_DTYPE_F32>(op, cblocks, st, off, B, V, F, slots, work, P, ldp, arg);
-    else if (dtype == SIR_DTYPE_BF16) launch_combine<SIR_DTYPE_BF16>(op, cblocks, st, off, B, V, F, slots, work, P, ldp, arg);
-    else launch_combine<SIR_DTYPE_F16>(op, cblocks, st, off, B, V, F, slots, work, P, ldp, arg);
-    return hipGetLastError();
+    return by_dtype(dtype, [&](auto dt) {
+        launch_combine<dt()>(op, cblocks, st, off, B, V, F, slots, work, P, ldp, arg);
+        return hipGetLastError();
+    });
 }
 
 hipError_t run_graph_pool_bwd(const int64_t* off, int64_t B, int64_t V, int F, int op, int dtype, const void* dP,
                               int64_t ldg, const int* arg, void* dX, int64_t lddx, hipStream_t st) {
     if (B == 0 || V == 0) return hipSuccess;
     const uintptr_t vb = dtype == SIR_DTYPE_F32 ? 16 : 8;
-    const bool v4 = F % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && al_to(dP, vb) && al_to(dX, vb) && al_to(arg, 16);
+    const bool v4 = F % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0 && aligned_to(dP, vb) && aligned_to(dX, vb) &&
+                    aligned16(arg);
     const int vw = v4 ? 4 : 1;
     const int n_cc = (F / vw + 63) / 64;
     const int64_t slots = graph_pool_slots(V, B);
     if (slots * n_cc > 0x7fffffffLL) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)(slots * n_cc);
-#define SIR_POOL_BWD(DT_)                                                                                          \
-    if (v4) launch_bwd<DT_, 4>(op, blocks, st, off, B, V, F, n_cc, slots, dP, ldg, arg, dX, lddx);                 \
-    else launch_bwd<DT_, 1>(op, blocks, st, off, B, V, F, n_cc, slots, dP, ldg, arg, dX, lddx);
-    if (dtype == SIR_DTYPE_F32) { SIR_POOL_BWD(SIR_DTYPE_F32) }
-    else if (dtype == SIR_DTYPE_BF16) { SIR_POOL_BWD(SIR_DTYPE_BF16) }
-    else { SIR_POOL_BWD(SIR_DTYPE_F16) }
-#undef SIR_POOL_BWD
-    return hipGetLastError();
+    return by_dtype(dtype, [&](auto dt) {
+        if (v4) launch_bwd<dt(), 4>(op, blocks, st, off, B, V, F, n_cc, slots, dP, ldg, arg, dX, lddx);
+        else launch_bwd<dt(), 1>(op, blocks, st, off, B, V, F, n_cc, slots, dP, ldg, arg, dX, lddx);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace sir

@@ -228,7 +228,8 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
-EDGE_SOURCES = ("sirconv_edge_impl.h", "sirconv_dropout.h", "sirconv_internal.h", "sirconv_dispatch.hip",
+EDGE_SOURCES = ("sirconv_edge_impl.h", "sirconv_device.h", "sirconv_dropout.h", "sirconv_internal.h",
+                "sirconv_dispatch.hip",
                 "sirconv_fwd_f32.hip", "sirconv_fwd_bf16.hip", "sirconv_fwd_f16.hip",
                 "sirconv_bwd_dual_f32.hip", "sirconv_bwd_dual_bf16.hip", "sirconv_bwd_dual_f16.hip")
 
@@ -575,15 +576,12 @@ def graph_norm_fwd(off, X, weight, bias, mean_scale, eps, Y, mean, std):
     _check(rc, lib)
 
 
-_DT_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}     # SIR_DTYPE_F32 / BF16 / F16
-
-
 def resid_act_fwd(Y, R, act, slope, order, out):
     """out = act(Y + R) (order 0) or act(Y) + R (order 1) in one pass (``sir_resid_act_fwd``)."""
     lib = load()
     M, N = Y.shape
     with _Timed("sir_resid_act_fwd", out.device):
-        rc = lib.sir_resid_act_fwd(_ptr(Y), Y.stride(0), _DT_CODE[Y.dtype], _ptr(R), R.stride(0), _ptr(out),
+        rc = lib.sir_resid_act_fwd(_ptr(Y), Y.stride(0), STORAGE[Y.dtype], _ptr(R), R.stride(0), _ptr(out),
                                    out.stride(0), M, N, int(act), float(slope), int(order), _stream(out.device))
     _check(rc, lib)
 
@@ -595,7 +593,7 @@ def resid_act_bwd(D, Y, R, act, slope, order, dY, dR=None, D2=None):
     M, N = Y.shape
     with _Timed("sir_resid_act_bwd", dY.device):
         rc = lib.sir_resid_act_bwd(_ptr(D), D.stride(0), _ptr(D2), D2.stride(0) if D2 is not None else 0,
-                                   _ptr(Y), Y.stride(0), _DT_CODE[Y.dtype], _ptr(R),
+                                   _ptr(Y), Y.stride(0), STORAGE[Y.dtype], _ptr(R),
                                    R.stride(0) if R is not None else 0, _ptr(dY), dY.stride(0), _ptr(dR),
                                    dR.stride(0) if dR is not None else 0, M, N, int(act), float(slope), int(order),
                                    _stream(dY.device))
